@@ -14,6 +14,14 @@ reference architecture.  Inputs are resident in HBM before timing starts.
 Launch: python bench.py [--gpus N --steps K --warmup W]; N>1 either via torch.distributed.run
 (WORLD_SIZE set: it must equal --gpus) or directly, in which case bench.py starts the N rank
 processes itself (one per GPU, RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up rollouts, the K timed rollouts
+(with the ensemble GEMMs' in-line timing, which costs no run of its own), the line.  --full adds
+the measurements that take runs of their own: the CPU baseline leg (sampler worker sweep + timed
+end-to-end runs on the host, before the GPU is touched) and, at N > 1, the untimed diagnostic
+rollouts that bracket the all-reduce.  --dump-outputs DIR writes what the last timed rollout
+returned to its caller as DIR/<name>.npy (dump_outputs below); the inputs are seeded, so two
+builds run with the same arguments can be compared array by array.
 """
 from __future__ import annotations
 
@@ -81,7 +89,14 @@ def parse():
                    help="ensemble GEMM: scaled 2-limb fp16 split (3 products) or 3-limb bf16 split (6 products) on "
                         "the 16-bit MFMA pipe (both fp32-level error), or f32 MFMA")
     p.add_argument("--expert-rows", type=int, default=50000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline leg (cpu_baseline in "
+                        "the line; --no-cpu-baseline skips it) and, at N > 1, the --diag-rollouts all-reduce "
+                        "diagnostics")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's outputs to DIR/<name>.npy (float32 / "
+                        "float64, <= 64 MB in all; the per-transition state rows as a fixed seeded sample)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     p.add_argument("--cpu-workers", type=int, default=0)
     p.add_argument("--cpu-samples", type=int, default=0,
                    help="env-steps per worker at each sweep point (default: sized for --cpu-point-s)")
@@ -129,7 +144,7 @@ def parse():
                    help="seconds a rendezvous or collective may block before the rank exits non-zero (the process "
                         "group's timeout; RCCL's watchdog tears the process down, TORCH_NCCL_ASYNC_ERROR_HANDLING=1)")
     p.add_argument("--diag-rollouts", type=int, default=5,
-                   help="N > 1: untimed rollouts after the timed region with the all-reduce bracketed by HIP events "
+                   help="--full, N > 1: untimed rollouts after the timed region with the all-reduce bracketed by HIP events "
                         "(the line's dist_diag.allreduce_wait_us)")
     return p.parse_args()
 
@@ -289,6 +304,81 @@ def plan_lanes(samples: int, max_lanes: int, lanes: int = 0):
     return best[1], best[2]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 4096
+
+
+def dump_outputs(out_dir: str, args, eng, cost, T: int, last: dict) -> dict:
+    """--dump-outputs: what the last timed rollout handed to its caller, as out_dir/<name>.npy
+    (float32, or float64 where the product holds float64).  Per-transition scalars (rewards,
+    ipm, bonus, disagreement, done) are written whole; the wide per-transition rows
+    (observations, next observations, actions) for DUMP_SAMPLE_ROWS transitions drawn once with
+    a fixed seed (their flat indices are sample_rows), and so is everything per-transition once
+    a rollout holds more than 2^20 of them.  Returns {name: shape}; at most DUMP_LIMIT_BYTES."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def sample(n):
+        if n <= DUMP_SAMPLE_ROWS:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.RandomState(20240229).choice(n, DUMP_SAMPLE_ROWS, replace=False)).astype(np.int64)
+
+    if args.mode == "paths":
+        paths = last["paths"]
+        n = sum(len(p["rewards"]) for p in paths)
+        rows = sample(n)
+        small = n <= (1 << 20)
+        arrays["path_lengths"] = np.asarray([len(p["rewards"]) for p in paths], dtype=np.float64)
+        rew = np.concatenate([np.asarray(p["rewards"], dtype=np.float32) for p in paths])
+        arrays["rewards"] = rew if small else rew[rows]
+        for key in ("observations", "next_observations", "actions"):
+            arrays[key] = np.concatenate([p[key] for p in paths])[rows].astype(np.float64)
+    else:
+        B, Bp = eng.B, eng.Bp
+        n = T * B
+        rows = sample(n)
+        small = n <= (1 << 20)
+        dev_rows = torch.from_numpy(rows).to(eng.obs.device)
+
+        def wide(x, w):  # [T, B, w] device -> the sampled transitions' rows
+            return x[:T].reshape(n, w)[dev_rows].cpu().numpy().astype(np.float64)
+
+        def scalar(x, ld, dt=np.float32):  # [T, ld] device (ld >= B: padded lanes dropped)
+            v = x[:T, :B].reshape(n)
+            return (v if small else v[dev_rows]).cpu().numpy().astype(dt)
+
+        arrays["observations"] = wide(eng.obs, eng.ctx.S)
+        arrays["next_observations"] = wide(eng.next_obs, eng.ctx.S)
+        arrays["actions"] = wide(eng.acts, eng.ctx.A)
+        arrays["done"] = scalar(eng.done, B)
+        arrays["rewards"] = scalar(eng.rewards, Bp)
+        arrays["disagreement"] = scalar(eng.disc, Bp)
+        if args.cost == "mmd":
+            arrays["ipm"] = scalar(eng.ipm, Bp)
+            arrays["bonus"] = scalar(eng.wbonus, Bp)
+            arrays["feature_sum"] = eng.phi_sum.cpu().numpy().astype(np.float64)
+            if eng.mb_mmd is not None:
+                arrays["mb_mmd"] = eng.mb_mmd.float().cpu().numpy().reshape(1)
+            if "expert_cost" in last:
+                arrays["expert_cost"] = last["expert_cost"].float().cpu().numpy().reshape(1)
+        if args.mode == "train":
+            adv = last["advantages"].reshape(n)
+            arrays["advantages"] = (adv if small else adv[dev_rows]).cpu().numpy().astype(np.float32)
+            arrays["policy_params"] = np.asarray(last["npg"].get_param_values(), dtype=np.float32)
+    arrays["sample_rows"] = rows.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -371,7 +461,7 @@ def main():
     S, A = (226, 28) if args.faithful else (197, 36)
 
     cpu_base = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline_leg(S, A, args)
 
     import numpy as np
@@ -461,13 +551,15 @@ def main():
     if shard:
         cost.shard_expert(rank, world, allreduce_async)
 
+    last = {}  # what the latest rollout handed back besides the engine's buffers (--dump-outputs)
+
     def one_rollout():
         eng.rollout(T)
         eng.relabel(allreduce)  # MMD: feature mean -> w -> rewards (GAIL: rewards already scored)
         if shard:
             cost.expert_allreduce()
         elif args.cost == "mmd":
-            cost.get_expert_cost()
+            last["expert_cost"] = cost.get_expert_cost()
         return T * B
 
     paths_info = {}
@@ -485,9 +577,10 @@ def main():
             eng.rollout(T)
             eng.relabel(allreduce)
             if args.cost == "mmd":
-                cost.get_expert_cost()
+                last["expert_cost"] = cost.get_expert_cost()
             adv = eng.advantages(baseline, gamma=0.995, gae_lambda=0.97)["advantages"]
             info = npg.train_from_engine(eng, adv)
+            last.update(advantages=adv, npg=npg)
             paths_info.update(kl=info["kl_dist"], alpha=info["alpha"])
             return T * B
 
@@ -506,6 +599,8 @@ def main():
             relabel_paths(paths, cost, ens, allreduce=allreduce)
             n = sum(len(p["rewards"]) for p in paths)
             paths_info.update(paths=len(paths), samples=n)
+            if args.dump_outputs:
+                last["paths"] = paths
             return n
 
     # the in-kernel GEMM timer is registered before the warm-up: graphs captured there (the
@@ -579,6 +674,10 @@ def main():
     elapsed = t1 - t0
     term_rate = float(eng.done[:T].float().mean().item()) if args.mode != "paths" else None
     own_elapsed = elapsed
+    # the last timed rollout's outputs, before anything below runs another rollout (rank 0's share)
+    dumped = None
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dumped = dump_outputs(args.dump_outputs, args, eng, cost, T, last)
     if world > 1:
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
@@ -614,7 +713,7 @@ def main():
     dist_diag = None
     if world > 1:
         wait_us = float("nan")
-        if args.diag_rollouts > 0 and args.mode == "engine" and not overlap:
+        if args.full and args.diag_rollouts > 0 and args.mode == "engine" and not overlap:
             ar_diag["on"] = True
             for _ in range(args.diag_rollouts):
                 one_rollout() if graph is None else graph()
@@ -718,7 +817,9 @@ def main():
                 "flops_per_launch": flops_per_fwd / per_fwd,
             },
             "step_flops_frac": round(value / world * step_flops / (peak * 1e12), 4),
+            "full": args.full,
             "cpu_baseline": cpu_base,
+            **({} if dumped is None else {"dump_outputs": {"dir": args.dump_outputs, "arrays": dumped}}),
             **({} if dist_diag is None else {"dist_diag": dist_diag}),
         }
         print(json.dumps(out), flush=True)

@@ -68,6 +68,18 @@ def test_hung_collective_times_out():
     assert ok.returncode == 0, ok.stderr[-2000:]  # no hung rank: the collective completes
 
 
+def test_plain_run_is_lean_by_default(monkeypatch):
+    """--full (the CPU baseline leg, the N > 1 diagnostics) and --dump-outputs are off unless asked for."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out" and not a.no_cpu_baseline
+
+
 def test_plan_lanes_per_rank_shares():
     """The lane x step plans of the 40 000-sample rollout per rank: lane counts that are
     multiples of 1024 in [4096, max_lanes] covering the share, and the shapes the GPU share tests

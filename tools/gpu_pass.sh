@@ -8,7 +8,7 @@
 # order given; the pass stops at the first failure, every GPU step under its own time limit):
 #   tests[:EXPR]   pytest -m gpu (EXPR: a -k expression; tests:FILE.py runs one file)
 #   smoke          __graft_entry__.smoke()
-#   bench          the default bench line (driver configuration: 20 steps, 5 warmup)
+#   bench          the bench line with the CPU baseline leg (bench.py --full; 20 steps, 5 warmup)
 #   prof           rocprofv3 --kernel-trace --stats of bench (no CPU leg) + the timed-region summary
 #   shares         the N = 8 / 4 per-rank share lines (5000 / 10000 samples)
 #   train          bench --mode train
@@ -34,7 +34,7 @@ for step in "$@"; do
         || { tail -20 "${O}_smoke.log"; exit 1; }
       tail -2 "${O}_smoke.log" ;;
     bench)
-      timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "${O}_bench.json" 2> "${O}_bench.err" \
+      timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "${O}_bench.json" 2> "${O}_bench.err" \
         || { tail -20 "${O}_bench.err"; exit 1; }
       cut -c1-300 "${O}_bench.json" ;;
     prof)
