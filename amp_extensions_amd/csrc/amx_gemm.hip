@@ -1,5 +1,11 @@
-// fp32 GEMM on CDNA4 matrix cores (v_mfma_f32_32x32x2_f32, exact f32 fma chains) with
-// fused epilogues for the hot path of the learned-dynamics rollout:
+// fp32-accurate GEMM on CDNA4 matrix cores with fused epilogues for the hot path of the
+// learned-dynamics rollout, in three precisions of the same contraction:
+//   * f32    (amx_gemm_*, amx_rff_features):       v_mfma_f32_32x32x2_f32, exact f32 fma chains
+//   * bf16x6 (amx_*_x6):   three bf16 limbs per operand, six limb products on 32x32x16_bf16
+//   * f16x3  (amx_*_h3, the default):  two scaled f16 limbs per operand, three limb products,
+//     on 32x32x16_f16 (plain double buffer: h3_tile_plain) or 16x16x32_f16 (split
+//     write-after-barrier schedule, stream-K: h3_tile_m16); tile families in amx_h3.h
+// The epilogues:
 //   * bias + ReLU written into a column slice of the dense-concat activation row
 //     (BasicMLP hidden layers, milo/milo/dynamics.py:427-430),
 //   * bias + output un-normalisation (milo/milo/dynamics.py:231-232),
@@ -9,7 +15,7 @@
 // C[r][n] = sum_k A[r][k] * W[n][k]: both operands are K-contiguous ("NT"), which is the
 // torch nn.Linear weight layout, so weights are used as stored.
 //
-// Tile family Tile<WM, WN, TM, TN>: WM x WN waves, each owning TM x TN MFMA 32x32 tiles, so
+// f32 tile family Tile<WM, WN, TM, TN>: WM x WN waves, each owning TM x TN MFMA 32x32 tiles, so
 // the workgroup tile is (32*WM*TM) x (32*WN*TN) with BK = 32.  Operands are register-staged
 // through LDS (double buffer, one barrier per K-tile, the next tile's global loads issued
 // before the MFMA block).  Lane l of an MFMA supplies k-slot h = l>>5; slot h of MFMA step s
@@ -62,18 +68,10 @@ struct Tile {
   static constexpr size_t LDS = 2 * STAGE * sizeof(float);  // double-buffered, 1 barrier / K-tile
   static constexpr int ROW_STEP = NT / 8;                   // staging rows covered per pass
   static constexpr int VA = BM / ROW_STEP, VW = BN / ROW_STEP;
+  static constexpr int RFF_ROWS = BM;                       // the RFF epilogue stages the whole tile
   static_assert(BM % ROW_STEP == 0 && BN % ROW_STEP == 0, "staging map");
   static_assert(LDS <= 160 * 1024, "LDS");
 };
-
-
-// LDS of the RFF epilogue: the staged BM x (BN + 4) f32 tile
-constexpr size_t rff_epi_lds(int bm, int bn) { return (size_t)bm * (bn + 4) * 4; }
-// rows of the M16 RFF epilogue's staging pass: the whole tile when its [BM][BN + 4] floats fit
-// 80 KB, else the largest multiple of 32 rows that does (the 160 x 256 tile: 64 rows)
-constexpr int rff_m16_rows(int bm, int bn) {
-  return rff_epi_lds(bm, bn) <= 80 * 1024 ? bm : (int)((80 * 1024) / ((size_t)(bn + 4) * 4 * 32)) * 32;
-}
 
 // ---- epilogue (shared by the f32 and the bf16x6 main loops: the 32x32 C/D register map
 // is dtype-independent on gfx950) ---------------------------------------------------------
@@ -87,61 +85,18 @@ __device__ __forceinline__ uint64_t row_valid_mask(const GemmArgs& a, int row0, 
   return __ballot(v);
 }
 
-// H3_EXP (diagnostic builds, bits): 1 = the split schedule's K-loop global loads left out (stale
-// tiles), 2 = the A limb split left out (raw bits published)
-#ifndef H3_EXP
-#define H3_EXP 0
-#endif
-// H3_ORDERED_LOADS (A/B builds: 0 = the scheduler's order): the f16x3 K loop's prologue issues
-// its staging loads in the loop's piece order (h3_tile's `load`)
-#ifndef H3_ORDERED_LOADS
-#define H3_ORDERED_LOADS 1
-#endif
-// H3_AFFINE (A/B builds: 0 = per-chunk offset registers): the 16x16x32 tiles' staging chunks j
-// sit NT / CPR rows apart, so a chunk's global offset is chunk 0's plus a wave-uniform step
-// (the buffer load's SGPR offset) and its LDS offset chunk 0's plus an immediate -- one
-// address register per operand instead of one per chunk
-#ifndef H3_AFFINE
-#define H3_AFFINE 1
-#endif
-// H3_W4 (A/B builds): the hidden layers' 256 x 256 tile on 4 waves of 128 x 128 (one wave per
-// SIMD, 256 accumulator registers each) instead of 8 waves of 128 x 64
-#ifndef H3_W4
-#define H3_W4 0
-#endif
-// OUT80 (A/B builds): 1 = the 80 x 224 output tile where it makes exactly one tile per CU
-#ifndef OUT80
-#define OUT80 1
-#endif
-// RFF_OCC3 (A/B builds): 1 = the RFF pass on 128 x 128 tiles at three workgroups per CU (H128rff3)
-// when its tiles exceed one round at two per CU
-#ifndef RFF_OCC3
-#define RFF_OCC3 1
-#endif
-// RFF_EXP (diagnostic builds, tools/src_variant.sh): 1 = no cos, 2 = no phi store
-#ifndef RFF_EXP
-#define RFF_EXP 0
-#endif
-// cos for the RFF epilogues.  RFF_HWCOS 1: z reduced to r in [-pi, pi] by a Cody-Waite step
-// (k = rint(z / 2 pi), 2 pi in three parts, fma), then the hardware v_cos_f32 on r / 2 pi; max
-// |error| 3.5e-7 against cos((double) z) over |z| <= 4096 (tools/cos_accuracy.hip,
-// profiles/r04o_cos_accuracy.txt: OCML cosf 7e-8), far below the fp32 rounding of the
-// argument itself (|z| 2^-24: 6e-6 at the MILO features' |z| ~ 1e2); |z| >= 2^16 takes cosf.
-// RFF_HWCOS 0: OCML cosf (rounds 1-3).
-#ifndef RFF_HWCOS
-#define RFF_HWCOS 1
-#endif
+// cos for the RFF epilogues: z reduced to r in [-pi, pi] by a Cody-Waite step (k = rint(z / 2 pi),
+// 2 pi in three parts, fma), then the hardware v_cos_f32 on r / 2 pi; max |error| 3.5e-7 against
+// cos((double) z) over |z| <= 4096 (tools/cos_accuracy.hip, profiles/r04o_cos_accuracy.txt: OCML
+// cosf 7e-8), far below the fp32 rounding of the argument itself (|z| 2^-24: 6e-6 at the MILO
+// features' |z| ~ 1e2); |z| >= 2^16 takes cosf.
 __device__ __forceinline__ float rff_cos(float z) {
-#if RFF_HWCOS
   if (__builtin_expect(__builtin_fabsf(z) >= 65536.0f, 0)) return cosf(z);
   const float k = __builtin_rintf(z * 0.15915494309189535f);
   float r = __builtin_fmaf(-k, 6.28318548202514648f, z);
   r = __builtin_fmaf(-k, -1.7484555314695172e-7f, r);
   r = __builtin_fmaf(-k, -2.3889859e-15f, r);
   return __builtin_amdgcn_cosf(r * 0.15915494309189535f);
-#else
-  return cosf(z);
-#endif
 }
 
 template <int EPI, class TL>
@@ -272,14 +227,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[TL::TM
         const int r = part * PR + i;
         const int row = tm * BM + r;
         const float z = Cs[r * CLD + c] + bv;       // nn.Linear: x W^T + b
-#if RFF_EXP == 1
-        const float phi = z * a.rff_scale;
-#else
         const float phi = rff_cos(z) * a.rff_scale;  // torch.cos(.) * np.sqrt(2/F)
-#endif
-#if RFF_EXP != 2
         Cg[(long long)row * a.ldc + col] = phi;
-#endif
         csum += ((vmask >> i) & 1u) ? (double)phi : 0.0;
       }
       a.col_partials[(long long)((tm * BM + part * PR) / AMX_RFF_PART_ROWS + q) * a.N + col] = csum;
@@ -417,6 +366,7 @@ struct TileX6 {
   static constexpr int NA = BM * (BK / 4);                     // 16-B chunks of the A tile (fp32)
   static constexpr int NW = BN * 6;                            // 16-B chunks of the W tile
   static constexpr int VA = (NA + NT - 1) / NT, VW = (NW + NT - 1) / NT;
+  static constexpr int RFF_ROWS = BM;                          // the RFF epilogue stages the whole tile (67.6 KB)
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
@@ -718,10 +668,10 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
   float* Cg = a.C + (long long)g * a.strideC;
   if constexpr (EPI == EPI_RFF) {  // the 32x32 path's RFF epilogue on the 16x16 accumulator layout
     // The tile staged through LDS in passes of RP rows (all of it when it fits the launch's
-    // LDS, rff_m16_rows), then one column per thread: the NT / BN threads of a column take the
+    // LDS, TL::RFF_ROWS), then one column per thread: the NT / BN threads of a column take the
     // 32-row groups g = part, part + NT / BN, ... (wave-uniform: BN >= 64), each group's phi
     // rows coalesced and its fp64 partial (AMX_RFF_PART_ROWS) summed in row order.
-    constexpr int BM = TL::BM, BN = TL::BN, CLD = BN + 4, P = TL::NT / BN, RP = rff_m16_rows(BM, BN);
+    constexpr int BM = TL::BM, BN = TL::BN, CLD = BN + 4, P = TL::NT / BN, RP = TL::RFF_ROWS;
     static_assert(TL::NT % BN == 0 && BN >= 64 && BM % AMX_RFF_PART_ROWS == 0 && RP % AMX_RFF_PART_ROWS == 0 &&
                       RP % 16 == 0, "RFF epilogue tiles");
     // un-scale in place (exact powers of two) while sExp (in the stage area) is readable
@@ -861,10 +811,41 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
   }
 }
 
-// One output tile (logical id `tile`, see map_tile; or, stream-K, the K-tiles [kb, ke) of it:
-// segment seg of nseg) of the f16x3 GEMM; the caller runs the timer hooks.
+// row exponents of the tile's A rows into sExp[0, BM): max over the slices this launch reads
+template <class TL>
+__device__ __forceinline__ void gather_row_exps(const GemmArgs& a, int g, int tm, int* sExp) {
+  const int* re = a.row_exp + (long long)g * a.strideRexp + (long long)tm * TL::BM;
+  const long long slot = (long long)a.tiles_m * TL::BM;  // slot stride = padded rows
+  for (int r = threadIdx.x; r < TL::BM; r += TL::NT) {
+    int e = -100;
+    for (int s = 0; s < a.rexp_slots; ++s) {
+      const int v = re[s * slot + r];
+      e = v > e ? v : e;
+    }
+    sExp[r] = e;
+  }
+}
+
+// SGPR descriptor of a panel for buffer loads: a per-thread byte offset plus the K-tile's byte
+// offset in an SGPR -- no 64-bit address VALU in the K loop (and 4 VGPRs fewer than per-thread W
+// pointers: the 256 x 256 tile's 44 B of scratch went with them)
+template <class T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t panel_rsrc(const T* p) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p), 0, 0x7ffffff0, 0x00020000);
+}
+
+// Staging maps of both tile loops: A chunk q = t + NT*j -> row q/CPR, k 4*(q%CPR); W chunk q ->
+// row q/CPR, 16-B piece q%CPR (the image's [granule][limb][16] order is the LDS row's order).
+// The loads of a K-tile are issued in the K loops' piece order (A chunks, then W chunks; each
+// pinned by a sched_barrier).  The compiler's waits at the loop head merge the prologue's
+// pending-load order with the back edge's: left to the scheduler, the prologue issued them in
+// reverse (A chunk 0 youngest), and the first publish of EVERY K-tile then waited vmcnt(0) -- for
+// all of the previous tile's loads, the W chunks issued just before the barrier included.
+
+// One output tile (logical id `tile`, see map_tile) of the f16x3 GEMM on the 32x32x16 form
+// (TileH3): plain double buffer, one barrier per K-tile.
 template <int EPI, class TL>
-__device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int ke, int seg, int nseg) {
+__device__ __forceinline__ void h3_tile_plain(const GemmArgs& a, int tile) {
   constexpr int BM = TL::BM, TM = TL::TM, TN = TL::TN, VA = TL::VA, VW = TL::VW, LD = TL::LD;
   constexpr int NT = TL::NT, STAGE = TL::STAGE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -883,24 +864,10 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
   const int wm = wave / TL::WN, wn = wave % TL::WN;
   const int li = lane & 31, lh = lane >> 5;
 
-  // row exponents of the tile's A rows: max over the slices this launch reads
-  {
-    const int* re = a.row_exp + (long long)g * a.strideRexp + (long long)tm * BM;
-    const long long slot = (long long)a.tiles_m * BM;  // slot stride = padded rows
-    for (int r = t; r < BM; r += NT) {
-      int e = -100;
-      for (int s = 0; s < a.rexp_slots; ++s) {
-        const int v = re[s * slot + r];
-        e = v > e ? v : e;
-      }
-      sExp[r] = e;
-    }
-  }
+  gather_row_exps<TL>(a, g, tm, sExp);
   __syncthreads();
   H3_STAMP(a, 1);
 
-  // staging maps: A chunk q = t + NT*j -> row q/CPR, k 4*(q%CPR); W chunk q -> row q/CPR,
-  // 16-B piece q%CPR (the image's [granule][limb][16] order is the LDS row's order)
   constexpr int CPR = TL::CPR, NSUB = TL::NSUB, BK = TL::BK;
   int a_src[VA];  // element offsets from the tile's first row (group g, or group 0 below k_shared)
   int a_dst[VA], a_sh[VA];
@@ -909,10 +876,10 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
 #pragma unroll
   for (int j = 0; j < VA; ++j) {
     const int q = t + NT * j;
-    a_ok[j] = (TL::NA % NT == 0 || j + 1 < VA) ? true : q < TL::NA;
+    a_ok[j] = (TL::NA % NT == 0 || j + 1 < VA) ? true : q < TL::NA;  // compile-time true but for a ragged last pass
     int r = a_ok[j] ? q / CPR : 0;
     const int c = q % CPR;
-    if constexpr (TL::AMAP && CPR == 8)  // chunks q>>5 -> 4 rows; lanes 0-7 r, 8-15 r+2, 16-23 r+1, 24-31 r+3
+    if constexpr (CPR == 8)  // A-map: chunks q>>5 -> 4 rows; lanes 0-7 r, 8-15 r+2, 16-23 r+1, 24-31 r+3
       r = a_ok[j] ? (q >> 5) * 4 + ((q >> 3) & 1) * 2 + ((q >> 4) & 1) : 0;
     a_src[j] = r * a.lda + 4 * c;
     a_dst[j] = r * LD + (c >> 2) * 32 + (c & 3) * 4;
@@ -929,229 +896,54 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
     w_off_b[j] = (int)(((long long)r * ldw2 + p * 8) * 2);
     w_dst[j] = BM * LD + r * LD + p * 8;
   }
+  const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(Ag), rsA0 = panel_rsrc(Ag0), rsW = panel_rsrc(Wg);
 
-  // buffer loads: SGPR descriptors for the tile's A panel (group g and group 0) and W panel, a
-  // per-thread byte offset and the K-tile's byte offset in an SGPR -- no 64-bit address VALU in
-  // the K loop (and 4 VGPRs fewer than per-thread W pointers: the 256 x 256 tile's 44 B of
-  // scratch went with them)
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Ag), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsA0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Ag0), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Wg), 0, 0x7ffffff0, 0x00020000);
-  // AFF: chunk j = chunk 0 + j * RSTEP rows (the plain map of the 16x16x32 tiles)
-  constexpr bool AFF = H3_AFFINE && TL::M16 && !TL::AMAP && TL::NA % NT == 0 && TL::NW % NT == 0;
-  constexpr int RSTEP = NT / CPR;
-  auto gA = [&](int j, int kt) -> f32x4 {
-    if constexpr (AFF)
-      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                           kt < nks ? rsA0 : rsA, a_src[0] * 4, (kt * BK + j * RSTEP * a.lda) * 4, 0));
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kt < nks ? rsA0 : rsA, a_src[j] * 4,
-                                                                          kt * BK * 4, 0));
-  };
-  auto gW = [&](int j, int kt) -> u32x4 {
-    if constexpr (AFF)
-      return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                           rsW, w_off_b[0], kt * 2 * BK * 2 + (int)(j * RSTEP * ldw2 * 2), 0));
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, w_off_b[j], kt * 2 * BK * 2, 0));
-  };
-  auto adst = [&](int j) { return AFF ? a_dst[0] + j * RSTEP * LD : a_dst[j]; };
-  auto wdst = [&](int j) { return AFF ? w_dst[0] + j * RSTEP * LD : w_dst[j]; };
-  f32x4 ra[TL::DEEPA ? 2 : 1][VA];  // A stage registers (DEEPA: the sets of tiles t+1 and t+2)
+  f32x4 ra[VA];
   u32x4 rw[VW];
-  constexpr int MB = TL::MB, NB = TL::NB;  // 16x16 blocks of the M16 form
-  using AccT = std::conditional_t<TL::M16, f32x4[MB][NB], f32x16[TM][TN]>;
-  AccT acc;
-  if constexpr (TL::M16) {
+  f32x16 acc[TM][TN];
 #pragma unroll
-    for (int i = 0; i < MB; ++i)
+  for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  } else {
+    for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  }
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   const int nk = a.K / BK;
-  auto load_a = [&](auto set, int kt) {
+  auto load = [&](int kt) {
     kt = kt < nk ? kt : nk - 1;  // past the end: re-read the last tile (branch-free)
 #pragma unroll
-    for (int j = 0; j < VA; ++j)
-      if (a_ok[j]) ra[decltype(set)::value][j] = gA(j, kt);
-  };
-  auto load_w = [&](int kt) {
-    kt = kt < nk ? kt : nk - 1;
+    for (int j = 0; j < VA; ++j) {
+      if (a_ok[j])
+        ra[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kt < nks ? rsA0 : rsA, a_src[j] * 4,
+                                                                                 kt * BK * 4, 0));
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
-    for (int j = 0; j < VW; ++j)
-      if (w_ok[j]) rw[j] = gW(j, kt);
-  };
-  // the prologue's loads in the K loop's piece order (A chunks, then W chunks; each pinned by a
-  // sched_barrier).  The compiler's waits at the loop head merge the prologue's pending-load
-  // order with the back edge's: left to the scheduler, the prologue issued them in reverse (A
-  // chunk 0 youngest), and the first publish of EVERY K-tile then waited vmcnt(0) -- for all
-  // of the previous tile's loads, the W chunks issued just before the barrier included.
-  // staging piece q: an A chunk or a W chunk (SPREAD with VA == VW alternates them, so every
-  // m-block carries one A split; otherwise the A chunks first)
-  constexpr bool ALT = TL::SPREAD && VA == VW;
-  auto piece_a = [](int q) { return ALT ? (q & 1) == 0 : q < VA; };
-  auto piece_j = [](int q) { return ALT ? q >> 1 : (q < VA ? q : q - VA); };
-  auto load = [&](int kt) {
-    kt = kt < nk ? kt : nk - 1;
-#pragma unroll
-    for (int q = 0; q < VA + VW; ++q) {
-      const int j = piece_j(q);
-      if (piece_a(q)) {
-        if (a_ok[j]) ra[0][j] = gA(j, kt);
-      } else {
-        if (w_ok[j]) rw[j] = gW(j, kt);
-      }
-      if constexpr (H3_ORDERED_LOADS) __builtin_amdgcn_sched_barrier(0);
+    for (int j = 0; j < VW; ++j) {
+      if (w_ok[j])
+        rw[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, w_off_b[j], kt * 2 * BK * 2, 0));
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
-  auto publish = [&](int base) {  // A from set 0
+  auto publish = [&](int base) {
 #pragma unroll
     for (int j = 0; j < VA; ++j)
       if (a_ok[j]) {
-        f32x4 x = ra[0][j];
-#if H3_EXP & 2
-        const u32x4 xb = __builtin_bit_cast(u32x4, x);
-        const u32x2 l0 = {xb[0], xb[1]}, l1 = {xb[2], xb[3]};
-#else
+        f32x4 x = ra[j];
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = __builtin_amdgcn_ldexpf(x[i], a_sh[j]);
         u32x2 l0, l1;
         split2(x, l0, l1);
-#endif
-        *reinterpret_cast<u32x2*>(sm + base + adst(j)) = l0;
-        *reinterpret_cast<u32x2*>(sm + base + adst(j) + 16) = l1;
+        *reinterpret_cast<u32x2*>(sm + base + a_dst[j]) = l0;
+        *reinterpret_cast<u32x2*>(sm + base + a_dst[j] + 16) = l1;
       }
 #pragma unroll
     for (int j = 0; j < VW; ++j)
-      if (w_ok[j]) *reinterpret_cast<u32x4*>(sm + base + wdst(j)) = rw[j];
-  };
-  // one staging piece (SPLIT): publish A/W chunk j of the registered tile, then reload chunk j
-  // of tile kt (clamped as load()); DEEPA: A chunk j of register set `set`, reloaded with tile
-  // kt + 1 (two tiles ahead of the W operand's one)
-  auto piece = [&](int q, int base, int kt, auto set) {
-    constexpr int SA = decltype(set)::value;
-    const int kta = TL::DEEPA ? (kt + 1 < nk ? kt + 1 : nk - 1) : (kt < nk ? kt : nk - 1);
-    kt = kt < nk ? kt : nk - 1;
-    if (q >= VA + VW) return;
-    if (piece_a(q)) {
-      const int j = piece_j(q);
-      if (a_ok[j]) {
-        f32x4 x = ra[SA][j];
-#if H3_EXP & 2
-        const u32x4 xb = __builtin_bit_cast(u32x4, x);
-        const u32x2 l0 = {xb[0], xb[1]}, l1 = {xb[2], xb[3]};
-#else
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[i] = __builtin_amdgcn_ldexpf(x[i], a_sh[j]);
-        u32x2 l0, l1;
-        split2(x, l0, l1);
-#endif
-        *reinterpret_cast<u32x2*>(sm + base + adst(j)) = l0;
-        *reinterpret_cast<u32x2*>(sm + base + adst(j) + 16) = l1;
-#if !(H3_EXP & 1)
-        ra[SA][j] = gA(j, kta);
-#endif
-      }
-    } else {
-      const int j = piece_j(q);
-      if (w_ok[j]) {
-        *reinterpret_cast<u32x4*>(sm + base + wdst(j)) = rw[j];
-#if !(H3_EXP & 1)
-        rw[j] = gW(j, kt);
-#endif
-      }
-    }
+      if (w_ok[j]) *reinterpret_cast<u32x4*>(sm + base + w_dst[j]) = rw[j];
   };
   const int a_off = (wm * TM * 32 + li) * LD + lh * 8;
   const int w_off = BM * LD + (wn * TN * 32 + li) * LD + lh * 8;
-  // M16: lane l reads row l&15 of a block, k = 8(l>>4)..+7 = granule l>>5, half (l>>4)&1
-  const int koff16 = (lane >> 5) * 32 + ((lane >> 4) & 1) * 8;
-  const int a_off16 = (wm * TL::WROWS + (lane & 15)) * LD + koff16;
-  const int w_off16 = BM * LD + (wn * TL::WCOLS + (lane & 15)) * LD + koff16;
-  f16x8 gb[NB][2], ga[2][2];
-  // the first fragments of the K-tile in buffer `base` (EARLY: issued right after the barrier,
-  // ahead of the LDS writes of the next tile, so the first MFMAs do not wait for those writes)
-  auto frag0 = [&](int base) {
-    if constexpr (TL::M16) {
-      const uint16_t* As = sm + base + a_off16;
-      const uint16_t* Ws = sm + base + w_off16;
-#pragma unroll
-      for (int n = 0; n < NB; ++n)
-#pragma unroll
-        for (int l = 0; l < 2; ++l) gb[n][l] = *reinterpret_cast<const f16x8*>(Ws + n * 16 * LD + l * 16);
-#pragma unroll
-      for (int l = 0; l < 2; ++l) ga[0][l] = *reinterpret_cast<const f16x8*>(As + l * 16);
-    }
-  };
-  int split_base = 0, split_kt = 0;  // SPLIT: where compute16's pieces publish / what they load
-  auto compute16 = [&](int base, auto set) {  // set: the A register set its pieces publish (DEEPA)
-    if constexpr (TL::M16) {
-    const uint16_t* As = sm + base + a_off16;
-    if constexpr (!TL::EARLY) frag0(base);
-    // the reads of block m+1 are pinned ahead of block m's MFMAs (sched_barrier): hipcc
-    // otherwise reloads one fragment register at a time and waits lgkmcnt(0) per MFMA group
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      if (m + 1 < MB) {
-#pragma unroll
-        for (int l = 0; l < 2; ++l)
-          ga[(m + 1) & 1][l] = *reinterpret_cast<const f16x8*>(As + (m + 1) * 16 * LD + l * 16);
-      }
-      if constexpr (TL::PIN && !TL::SPREAD) __builtin_amdgcn_sched_barrier(0);
-      constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // small terms first
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int n = 0; n < NB; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[m & 1][PA[p]], gb[n][PB[p]], acc[m][n], 0, 0, 0);
-      if constexpr (TL::PIN && !TL::SPREAD) __builtin_amdgcn_sched_barrier(0);
-      if constexpr (TL::SPREAD) {
-        // one wave per SIMD: no partner wave covers the staging work, so it is interleaved into
-        // the block's MFMA stream (sched_group_barrier: MFMA / DS read / VALU / DS write / VMEM)
-        constexpr int PPB = (VA + VW + MB - 1) / MB;
-#pragma unroll
-        for (int q = m * PPB; q < (m + 1) * PPB; ++q) piece(q, split_base, split_kt, set);
-        constexpr int NMF = 3 * NB;
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < PPB; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - 14 - 2 * PPB, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (TL::SPLIT) {
-        piece(m, split_base, split_kt, set);
-        if (m == MB - 1) {
-#pragma unroll
-          for (int q = MB; q < VA + VW; ++q) piece(q, split_base, split_kt, set);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    }
-  };
   auto compute = [&](int base) {
-    if constexpr (TL::M16) {
-      compute16(base, std::integral_constant<int, 0>{});
-      return;
-    } else {
     const uint16_t* As = sm + base + a_off;
     const uint16_t* Ws = sm + base + w_off;
     // m-outer order: the W fragments of the granule stay in registers, the A fragments of
@@ -1174,7 +966,6 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
           for (int l = 0; l < 2; ++l)
             fa[(m + 1) & 1][l] = *reinterpret_cast<const f16x8*>(As + (m + 1) * 32 * LD + sub * 32 + l * 16);
         }
-        if constexpr (TL::PIN) __builtin_amdgcn_sched_barrier(0);
         // small terms first: (a1,b0) (a0,b1) (a0,b0)
         constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
 #pragma unroll
@@ -1182,110 +973,10 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
 #pragma unroll
           for (int n = 0; n < TN; ++n)
             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[m & 1][PA[p]], fb[n][PB[p]], acc[m][n], 0, 0, 0);
-        if constexpr (TL::PIN) __builtin_amdgcn_sched_barrier(0);
       }
-    }
     }
   };
 
-  auto finish = [&](AccT& ac) {
-    if constexpr (TL::M16) {
-      // the row exponents lived in stage buffer 1 during the prologue; re-read them into LDS
-      __syncthreads();
-      sExp = reinterpret_cast<int*>(sm);
-      const int* re = a.row_exp + (long long)g * a.strideRexp + (long long)tm * BM;
-      const long long slot = (long long)a.tiles_m * BM;
-      for (int r = t; r < BM; r += NT) {
-        int e = -100;
-        for (int s2 = 0; s2 < a.rexp_slots; ++s2) {
-          const int v = re[s2 * slot + r];
-          e = v > e ? v : e;
-        }
-        sExp[r] = e;
-      }
-      __syncthreads();
-      epilogue_h3_m16<EPI, TL>(a, ac, sExp, g, tm, tn);
-    } else {
-      epilogue_h3<EPI, TL>(a, ac, sExp, g, tm, tn);
-    }
-  };
-  if constexpr (TL::DEEPA) {
-    // K-tiles [kb, ke); tile x's A in register set (x - kb) & 1, loaded two tiles ahead
-    load(kb);
-    publish(0);
-    load_a(std::integral_constant<int, 1>{}, kb + 1);
-    load_w(kb + 1);
-    load_a(std::integral_constant<int, 0>{}, kb + 2);
-    H3_STAMP(a, 2);
-    auto kstep = [&](int kt, auto par) {  // buffer par; pieces publish tile kt+1 from set par^1
-      constexpr int P = decltype(par)::value;
-      __syncthreads();  // tile kt visible in buffer P; buffer P^1 (tile kt-1) fully read
-      frag0(P * STAGE);
-      __builtin_amdgcn_sched_barrier(0);
-      split_base = (P ^ 1) * STAGE;
-      split_kt = kt + 2;
-      compute16(P * STAGE, std::integral_constant<int, P ^ 1>{});
-    };
-    for (int kt = kb; kt < ke; kt += 2) {
-      kstep(kt, std::integral_constant<int, 0>{});
-      if (kt + 1 < ke) kstep(kt + 1, std::integral_constant<int, 1>{});
-    }
-    H3_STAMP(a, 3);
-    if constexpr (EPI == EPI_UNNORM) {
-      if (nseg > 1) {
-        __syncthreads();  // the stage buffers are free: one int of LDS for the last-arriver flag
-        if (!split_combine<TL>(a, acc, tile, seg, nseg, reinterpret_cast<int*>(smem) + BM + 4)) return;
-      }
-    }
-    finish(acc);
-#if H3_TRACE
-    H3_STAMP(a, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    H3_STAMP(a, 5);
-#endif
-    return;
-  }
-  if constexpr (TL::LATE) {
-    // K-tiles [kb, ke) of this workgroup (all of them unless the tile is split)
-    load(kb);
-    publish(0);
-    load(kb + 1);
-    H3_STAMP(a, 2);
-    for (int kt = kb; kt < ke; ++kt) {
-      const int cur = (kt - kb) & 1;
-      __syncthreads();  // tile kt visible in buffer cur; buffer cur^1 (tile kt-1) fully read
-      if constexpr (TL::EARLY) {
-        frag0(cur * STAGE);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (TL::SPLIT) {  // tile kt+1's publish and tile kt+2's loads run inside compute
-        split_base = (cur ^ 1) * STAGE;
-        split_kt = kt + 2;
-        compute(cur * STAGE);
-        continue;
-      }
-      publish((cur ^ 1) * STAGE);  // tile kt+1 (past the end: a harmless re-publish)
-      load(kt + 2);
-      __builtin_amdgcn_sched_barrier(0);
-      compute(cur * STAGE);
-    }
-    H3_STAMP(a, 3);
-    // (the 256 x 256 hidden tile is launched one tile per workgroup only: no combine code, whose
-    // registers it cannot spare)
-    if constexpr (TL::M16 && (EPI == EPI_UNNORM || (EPI == EPI_BIAS_ACT && !(BM == 256 && TL::BN == 256)))) {
-      if (nseg > 1) {
-        __syncthreads();  // the stage buffers are free: one int of LDS for the last-arriver flag
-        if (!split_combine<TL>(a, acc, tile, seg, nseg, reinterpret_cast<int*>(smem) + BM + 4)) return;
-      }
-    }
-    finish(acc);
-#if H3_TRACE
-    H3_STAMP(a, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    H3_STAMP(a, 5);
-#endif
-    return;
-  }
   load(0);
   publish(0);
   __syncthreads();
@@ -1297,10 +988,268 @@ __device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int
     publish((cur ^ 1) * STAGE);
     __syncthreads();
   }
-  finish(acc);
+  epilogue_h3<EPI, TL>(a, acc, sExp, g, tm, tn);
 }
 
-// a.streamk (LATE M16 UNNORM tiles): one workgroup per CU; the workgroups of one XCD take
+// One output tile (or, stream-K, the K-tiles [kb, ke) of it: segment seg of nseg) of the f16x3
+// GEMM on the 16x16x32 form (TileH3M16): split write-after-barrier schedule; the caller runs the
+// timer hooks.
+template <int EPI, class TL>
+__device__ __forceinline__ void h3_tile_m16(const GemmArgs& a, int tile, int kb, int ke, int seg, int nseg) {
+  constexpr int BM = TL::BM, MB = TL::MB, NB = TL::NB, VA = TL::VA, VW = TL::VW, LD = TL::LD;
+  constexpr int NT = TL::NT, STAGE = TL::STAGE;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  uint16_t* const sm = reinterpret_cast<uint16_t*>(smem);
+  int* sExp = reinterpret_cast<int*>(sm + TL::SEXP);  // in stage buffer 1 until the loop's first publish
+  int g, tm, tn;
+  tile_coords(a, tile, g, tm, tn);
+  const float* __restrict__ Ag = a.A + (long long)g * a.strideA + (long long)tm * BM * a.lda;
+  const float* __restrict__ Ag0 = a.A + (long long)tm * BM * a.lda;  // group 0: the shared K slice
+  const long long ldw2 = 2LL * a.K;
+  const uint16_t* __restrict__ Wg = a.W2 + (long long)g * a.strideW2 + (long long)tn * TL::BN * ldw2;
+
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int wave = t >> 6;
+  const int wm = wave / TL::WN, wn = wave % TL::WN;
+
+  gather_row_exps<TL>(a, g, tm, sExp);
+  __syncthreads();
+  H3_STAMP(a, 1);
+
+  // AFF (tiles whose chunks fill whole passes of the workgroup): chunk j = chunk 0 + j * RSTEP
+  // rows, so a chunk's global offset is chunk 0's plus a wave-uniform step (the buffer load's SGPR
+  // offset) and its LDS offset chunk 0's plus an immediate -- one address register per operand
+  // instead of one per chunk.  The other tiles keep per-chunk offsets.
+  constexpr int CPR = TL::CPR, BK = TL::BK, RSTEP = NT / CPR;
+  constexpr bool AFF = TL::NA % NT == 0 && TL::NW % NT == 0;
+  int a_src[VA];  // element offsets from the tile's first row (group g, or group 0 below k_shared)
+  int a_dst[VA], a_sh[VA];
+  bool a_ok[VA];
+  const int nks = a.k_shared / BK;
+#pragma unroll
+  for (int j = 0; j < VA; ++j) {
+    const int q = t + NT * j;
+    a_ok[j] = (TL::NA % NT == 0 || j + 1 < VA) ? true : q < TL::NA;  // compile-time true but for a ragged last pass
+    const int r = a_ok[j] ? q / CPR : 0, c = q % CPR;
+    a_src[j] = r * a.lda + 4 * c;
+    a_dst[j] = r * LD + (c >> 2) * 32 + (c & 3) * 4;
+    a_sh[j] = HSC - sExp[r];
+  }
+  int w_off_b[VW];  // byte offsets from the tile's first weight row
+  int w_dst[VW];
+  bool w_ok[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+    const int q = t + NT * j;
+    w_ok[j] = (TL::NW % NT == 0 || j + 1 < VW) ? true : q < TL::NW;
+    const int r = w_ok[j] ? q / CPR : 0, p = q % CPR;
+    w_off_b[j] = (int)(((long long)r * ldw2 + p * 8) * 2);
+    w_dst[j] = BM * LD + r * LD + p * 8;
+  }
+  const __amdgpu_buffer_rsrc_t rsA = panel_rsrc(Ag), rsA0 = panel_rsrc(Ag0), rsW = panel_rsrc(Wg);
+  auto gA = [&](int j, int kt) -> f32x4 {
+    if constexpr (AFF)
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                           kt < nks ? rsA0 : rsA, a_src[0] * 4, (kt * BK + j * RSTEP * a.lda) * 4, 0));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(kt < nks ? rsA0 : rsA, a_src[j] * 4,
+                                                                          kt * BK * 4, 0));
+  };
+  auto gW = [&](int j, int kt) -> u32x4 {
+    if constexpr (AFF)
+      return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                           rsW, w_off_b[0], kt * 2 * BK * 2 + (int)(j * RSTEP * ldw2 * 2), 0));
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, w_off_b[j], kt * 2 * BK * 2, 0));
+  };
+  auto adst = [&](int j) { return AFF ? a_dst[0] + j * RSTEP * LD : a_dst[j]; };
+  auto wdst = [&](int j) { return AFF ? w_dst[0] + j * RSTEP * LD : w_dst[j]; };
+  f32x4 ra[TL::DEEPA ? 2 : 1][VA];  // A stage registers (DEEPA: the sets of tiles t+1 and t+2)
+  u32x4 rw[VW];
+  f32x4 acc[MB][NB];
+#pragma unroll
+  for (int i = 0; i < MB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = a.K / BK;
+  auto load_a = [&](auto set, int kt) {
+    kt = kt < nk ? kt : nk - 1;  // past the end: re-read the last tile (branch-free)
+#pragma unroll
+    for (int j = 0; j < VA; ++j)
+      if (a_ok[j]) ra[decltype(set)::value][j] = gA(j, kt);
+  };
+  auto load_w = [&](int kt) {
+    kt = kt < nk ? kt : nk - 1;
+#pragma unroll
+    for (int j = 0; j < VW; ++j)
+      if (w_ok[j]) rw[j] = gW(j, kt);
+  };
+  auto load = [&](int kt) {  // a whole K-tile (A into set 0) in piece order
+    kt = kt < nk ? kt : nk - 1;
+#pragma unroll
+    for (int j = 0; j < VA; ++j) {
+      if (a_ok[j]) ra[0][j] = gA(j, kt);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      if (w_ok[j]) rw[j] = gW(j, kt);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // A chunk j scaled by its row's 2^(14 - E_r), split, the limbs stored in the buffer at `base`
+  auto put_a = [&](int base, int j, f32x4 x) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = __builtin_amdgcn_ldexpf(x[i], a_sh[j]);
+    u32x2 l0, l1;
+    split2(x, l0, l1);
+    *reinterpret_cast<u32x2*>(sm + base + adst(j)) = l0;
+    *reinterpret_cast<u32x2*>(sm + base + adst(j) + 16) = l1;
+  };
+  auto publish = [&](int base) {  // A from set 0
+#pragma unroll
+    for (int j = 0; j < VA; ++j)
+      if (a_ok[j]) put_a(base, j, ra[0][j]);
+#pragma unroll
+    for (int j = 0; j < VW; ++j)
+      if (w_ok[j]) *reinterpret_cast<u32x4*>(sm + base + wdst(j)) = rw[j];
+  };
+  // one staging piece q (the A chunks, then the W chunks): publish chunk j of the registered tile
+  // into the buffer at `base`, then reload chunk j of tile kt (clamped as load()); DEEPA: A chunk
+  // j of register set `set`, reloaded with tile kt + 1 (two tiles ahead of the W operand's one)
+  auto piece = [&](int q, int base, int kt, auto set) {
+    constexpr int SA = decltype(set)::value;
+    const int kta = TL::DEEPA ? (kt + 1 < nk ? kt + 1 : nk - 1) : (kt < nk ? kt : nk - 1);
+    kt = kt < nk ? kt : nk - 1;
+    if (q >= VA + VW) return;
+    if (q < VA) {
+      if (a_ok[q]) {
+        put_a(base, q, ra[SA][q]);
+        ra[SA][q] = gA(q, kta);
+      }
+    } else {
+      const int j = q - VA;
+      if (w_ok[j]) {
+        *reinterpret_cast<u32x4*>(sm + base + wdst(j)) = rw[j];
+        rw[j] = gW(j, kt);
+      }
+    }
+  };
+  // lane l reads row l&15 of a block, k = 8(l>>4)..+7 = granule l>>5, half (l>>4)&1
+  const int koff16 = (lane >> 5) * 32 + ((lane >> 4) & 1) * 8;
+  const int a_off16 = (wm * TL::WROWS + (lane & 15)) * LD + koff16;
+  const int w_off16 = BM * LD + (wn * TL::WCOLS + (lane & 15)) * LD + koff16;
+  f16x8 gb[NB][2], ga[2][2];
+  // the first fragments of the K-tile in buffer `base`: issued right after the barrier, ahead of
+  // the LDS writes of the next tile, so the first MFMAs do not wait for those writes
+  auto frag0 = [&](int base) {
+    const uint16_t* As = sm + base + a_off16;
+    const uint16_t* Ws = sm + base + w_off16;
+#pragma unroll
+    for (int n = 0; n < NB; ++n)
+#pragma unroll
+      for (int l = 0; l < 2; ++l) gb[n][l] = *reinterpret_cast<const f16x8*>(Ws + n * 16 * LD + l * 16);
+#pragma unroll
+    for (int l = 0; l < 2; ++l) ga[0][l] = *reinterpret_cast<const f16x8*>(As + l * 16);
+  };
+  // the MFMAs of the K-tile in buffer `base` (after frag0); behind each m-block's MFMAs one
+  // staging piece (the rest behind the last block): they publish into the buffer at `pub` from A
+  // register set `set` and load tile `ktn`
+  auto compute16 = [&](int base, int pub, int ktn, auto set) {
+    const uint16_t* As = sm + base + a_off16;
+    // the reads of block m+1 are pinned ahead of block m's MFMAs (sched_barrier): hipcc
+    // otherwise reloads one fragment register at a time and waits lgkmcnt(0) per MFMA group
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      if (m + 1 < MB) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l)
+          ga[(m + 1) & 1][l] = *reinterpret_cast<const f16x8*>(As + (m + 1) * 16 * LD + l * 16);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};  // small terms first
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int n = 0; n < NB; ++n)
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[m & 1][PA[p]], gb[n][PB[p]], acc[m][n], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      piece(m, pub, ktn, set);
+      if (m == MB - 1) {
+#pragma unroll
+        for (int q = MB; q < VA + VW; ++q) piece(q, pub, ktn, set);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  // compute16 with the one register set of the one-ahead loop
+  auto compute = [&](int base, int pub, int ktn) { compute16(base, pub, ktn, std::integral_constant<int, 0>{}); };
+
+  // K-tiles [kb, ke) of this workgroup (all of them unless the tile is split)
+  load(kb);
+  publish(0);
+  if constexpr (TL::DEEPA) {
+    // tile x's A in register set (x - kb) & 1, loaded two tiles ahead
+    load_a(std::integral_constant<int, 1>{}, kb + 1);
+    load_w(kb + 1);
+    load_a(std::integral_constant<int, 0>{}, kb + 2);
+    H3_STAMP(a, 2);
+    auto kstep = [&](int kt, auto par) {  // buffer par; pieces publish tile kt+1 from set par^1
+      constexpr int P = decltype(par)::value;
+      __syncthreads();  // tile kt visible in buffer P; buffer P^1 (tile kt-1) fully read
+      frag0(P * STAGE);
+      __builtin_amdgcn_sched_barrier(0);
+      compute16(P * STAGE, (P ^ 1) * STAGE, kt + 2, std::integral_constant<int, P ^ 1>{});
+    };
+    for (int kt = kb; kt < ke; kt += 2) {
+      kstep(kt, std::integral_constant<int, 0>{});
+      if (kt + 1 < ke) kstep(kt + 1, std::integral_constant<int, 1>{});
+    }
+  } else {
+    load(kb + 1);
+    H3_STAMP(a, 2);
+    for (int kt = kb; kt < ke; ++kt) {
+      const int cur = (kt - kb) & 1;
+      __syncthreads();  // tile kt visible in buffer cur; buffer cur^1 (tile kt-1) fully read
+      frag0(cur * STAGE);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(cur * STAGE, (cur ^ 1) * STAGE, kt + 2);  // with tile kt+1's publish and tile kt+2's loads
+    }
+  }
+  H3_STAMP(a, 3);
+  // (the 256 x 256 hidden tile is launched one tile per workgroup only: no combine code, whose
+  // registers it cannot spare)
+  if constexpr (EPI == EPI_UNNORM || (EPI == EPI_BIAS_ACT && !(BM == 256 && TL::BN == 256))) {
+    if (nseg > 1) {
+      __syncthreads();  // the stage buffers are free: one int of LDS for the last-arriver flag
+      if (!split_combine<TL>(a, acc, tile, seg, nseg, reinterpret_cast<int*>(smem) + BM + 4)) return;
+    }
+  }
+  // the row exponents lived in stage buffer 1 during the prologue; re-read them into LDS
+  __syncthreads();
+  sExp = reinterpret_cast<int*>(sm);
+  gather_row_exps<TL>(a, g, tm, sExp);
+  __syncthreads();
+  epilogue_h3_m16<EPI, TL>(a, acc, sExp, g, tm, tn);
+#if H3_TRACE
+  H3_STAMP(a, 4);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  H3_STAMP(a, 5);
+#endif
+}
+
+// The tile loop of the tile's family (a 32x32x16 tile always runs its whole K range: those tiles
+// are never launched stream-K).
+template <int EPI, class TL>
+__device__ __forceinline__ void h3_tile(const GemmArgs& a, int tile, int kb, int ke, int seg, int nseg) {
+  if constexpr (TL::M16)
+    h3_tile_m16<EPI, TL>(a, tile, kb, ke, seg, nseg);
+  else
+    h3_tile_plain<EPI, TL>(a, tile);
+}
+
+// a.streamk (16x16x32 tiles): one workgroup per CU; the workgroups of one XCD take
 // consecutive virtual ids v (xcd_logical) and v runs the K-tiles [v U / G, (v + 1) U / G) of
 // the U = tiles x nk units in logical tile order (tile_n fastest, then tile_m: an XCD's
 // workgroups share A row panels and one member's weight panels in its L2) -- one, two or three
@@ -1396,22 +1345,19 @@ __global__ __launch_bounds__(256) void k_row_exp(const float* __restrict__ A, in
 // The tiles the launchers pick (chosen by same-process A/B runs in round 1: DESIGN.md §3.0,
 // profiles/r01_h3_*.txt):
 //   hidden layers, grid >= one WG per CU: 256x256, BK 32, 8 waves of 128x64 on 16x16x32,
-//     write-after-barrier with pinned / early fragment reads and split staging (160 KB LDS)
+//     split write-after-barrier schedule (160 KB LDS)
 //   otherwise (and the RFF features): 128x128, BK 32, 4 waves of 64x64 on 32x32x16
 //   output layer S <= 224: 128x224, 14 waves of 64x32 on 16x16x32 (same schedule);
 //     S in (224, 256]: 128x256, 8 waves of 64x64
-using H256 = TileH3<2, 4, 4, 2, 2, 2, true, true, true, 0, 0, true, true, true>;
-// 4 waves of 128 x 128, one per SIMD (H3_W4 A/B): 192 MFMAs and 32 fragment reads per wave and
-// K-tile, the 16 staging pieces two behind each m-block
-using H256w4 = TileH3<2, 2, 4, 4, 1, 2, true, true, true, 0, 0, true, true, true, false, true>;
+using H256 = TileH3M16<2, 4, 8, 4>;
 // row-block tiles for the strong-scaling lane counts (rows = 32 RB, 4 members: a 256-workgroup
 // grid for every RB): hidden RB x 256 (8 waves of RB/2 x 64), output RB x 112 / RB x 128
 // (RB/32 waves of 32 x 112 or 32 x 128), same schedule as H256
-template <int MB> using HRow = TileH3<2, 4, 1, 1, 2, 2, true, true, true, MB, 4, true, true, true>;
-template <int RW, int NBO> using HOut = TileH3<RW, 1, 1, 1, 2, 2, true, true, true, 2, NBO, true, true, true>;
+template <int MB> using HRow = TileH3M16<2, 4, MB, 4>;
+template <int RW, int NBO> using HOut = TileH3M16<RW, 1, 2, NBO>;
 using H128k32 = TileH3<2, 2, 2, 2, 2, 2>;
 // the RFF pass's 128 x 128 tile at three workgroups per CU: BK 16 (41.5 KB of stage buffers),
-// the epilogue staged in two 64-row passes (RFF_OCC3)
+// the epilogue staged in two 64-row passes
 using H128rff3 = TileH3<2, 2, 2, 2, 3, 1>;
 // RFF features at row counts whose 128 x 128 tiles fill less than the CUs (the 4- and 8-GPU
 // strong-scaling shares): 128 x 64, 4 waves of 32 x 64 (half the work per workgroup, twice
@@ -1424,16 +1370,14 @@ using H128 = TileH3<2, 2, 2, 2>;  // K not a multiple of 32 (BK 16)
 // 88.5 -> 76.2 us under rocprofv3, same box (profiles/r05e_rff160_ab.txt).  (A 160 x 64 tile,
 // 4 waves of 80 x 32 at two per CU -- 5120 rows in one round of 256 tiles -- took 25.1 us
 // against the 128 x 64 tile's 23.1 and was dropped.)
-using H160x256r = TileH3<2, 4, 1, 1, 1, 2, true, true, true, 5, 4, true, true, true>;
-using H128x224 = TileH3<2, 7, 2, 1, 4, 2, true, true, true, 0, 0, true, true, true, true>;  // + DEEPA (-2 %)
-// 80 x 224 output tiles, 7 waves of 80 x 32 (16x16x32 form, split schedule): one tile per CU when
-// groups * rows / 80 == CUs (5120 lanes x 4 members: the N = 4 / 8 per-rank shares) -- no
-// stream-K partial tiles, the A panel read once
-using H80x224 = TileH3<1, 7, 1, 1, 1, 2, true, true, true, 5, 2, true, true, true, true>;  // + DEEPA
-
-
+using H160x256r = TileH3M16<2, 4, 5, 4, 1>;
+using H128x224 = TileH3M16<2, 7, 4, 2, 4, true>;  // DEEPA (-2 %)
+// 80 x 224 output tiles, 7 waves of 80 x 32 (DEEPA): one tile per CU when groups * rows / 80 ==
+// CUs (5120 lanes x 4 members: the N = 4 / 8 per-rank shares) -- no stream-K partial tiles, the
+// A panel read once
+using H80x224 = TileH3M16<1, 7, 5, 2, 1, true>;
 using H128x224k16 = TileH3<2, 7, 2, 1, 4>;  // K not a multiple of 32
-using H128x256 = TileH3<2, 4, 2, 2, 2, 2, true, true, true, 0, 0, true, true, true>;
+using H128x256 = TileH3M16<2, 4, 4, 4>;
 // small-row tiles (the reference-semantics sampler: a few hundred lanes, or 128 per member when
 // each lane runs its own member only): 128 x 64 hidden tiles (4 waves of 64 x 32) and 128 x 32
 // output tiles (4 waves of 32 x 32), stream-K over up to one workgroup per CU (small_plan) --
@@ -1441,10 +1385,31 @@ using H128x256 = TileH3<2, 4, 2, 2, 2, 2, true, true, true, 0, 0, true, true, tr
 // 8 waves (two per SIMD: one wave's staging overlaps the other's MFMAs) when a member has one
 // 128-row tile (the member-blocked sampler's 512 lanes: forward 75 -> 68 us), else 4 waves
 // (256+ rows: 85 vs 90 us at 1024 lanes; profiles/r06y_small_tile_waves_ab.txt)
-using HS64 = TileH3<2, 2, 1, 1, 2, 2, true, true, true, 4, 2, true, true, true>;
-using HS64w8 = TileH3<4, 2, 1, 1, 2, 2, true, true, true, 2, 2, true, true, true>;
-using HS32 = TileH3<4, 1, 1, 1, 2, 2, true, true, true, 2, 2, true, true, true>;
-using HS32w8 = TileH3<8, 1, 1, 1, 2, 2, true, true, true, 1, 2, true, true, true>;
+using HS64 = TileH3M16<2, 2, 4, 2>;
+using HS64w8 = TileH3M16<4, 2, 2, 2>;
+using HS32 = TileH3M16<4, 1, 2, 2>;
+using HS32w8 = TileH3M16<8, 1, 1, 2>;
+
+// the shape of every alias as it was under the one 16-parameter tile template
+template <class TL>
+constexpr bool tile_is(int bm, int bn, int nt, size_t lds) {
+  return TL::BM == bm && TL::BN == bn && TL::NT == nt && TL::LDS == lds;
+}
+static_assert(tile_is<H256>(256, 256, 512, 163840), "H256");
+static_assert(tile_is<HRow<4>>(128, 256, 512, 122880) && tile_is<HRow<5>>(160, 256, 512, 133120) &&
+                  tile_is<HRow<6>>(192, 256, 512, 143360) && tile_is<HRow<7>>(224, 256, 512, 153600), "HRow");
+static_assert(tile_is<HOut<4, 7>>(128, 112, 256, 76800) && tile_is<HOut<5, 7>>(160, 112, 320, 87040) &&
+                  tile_is<HOut<6, 7>>(192, 112, 384, 97280) && tile_is<HOut<7, 7>>(224, 112, 448, 107520), "HOut 112");
+static_assert(tile_is<HOut<4, 8>>(128, 128, 256, 81920) && tile_is<HOut<5, 8>>(160, 128, 320, 92160) &&
+                  tile_is<HOut<6, 8>>(192, 128, 384, 102400) && tile_is<HOut<7, 8>>(224, 128, 448, 112640), "HOut 128");
+static_assert(tile_is<H160x256r>(160, 256, 512, 133120), "H160x256r");
+static_assert(tile_is<H128x224>(128, 224, 896, 112640) && tile_is<H80x224>(80, 224, 448, 97280), "DEEPA tiles");
+static_assert(tile_is<H128x256>(128, 256, 512, 122880), "H128x256");
+static_assert(tile_is<HS64>(128, 64, 256, 61440) && tile_is<HS64w8>(128, 64, 512, 61440) &&
+                  tile_is<HS32>(128, 32, 256, 51200) && tile_is<HS32w8>(128, 32, 512, 51200), "small-row tiles");
+static_assert(tile_is<H128>(128, 128, 256, 41472) && tile_is<H128k32>(128, 128, 256, 74240) &&
+                  tile_is<H128rff3>(128, 128, 256, 41472) && tile_is<H128x64k32>(128, 64, 256, 55808) &&
+                  tile_is<H128x224k16>(128, 224, 896, 56832), "32x32x16 tiles");
 
 using X128 = TileX6<2, 2, 2, 2>;        // 128x128, 4 waves of 64x64 (57 KB): 2 WGs / CU
 using X256 = TileX6<2, 4, 4, 2>;        // 256x256, 8 waves of 128x64 (115 KB): 1 WG / CU
@@ -1461,83 +1426,56 @@ int resident_wgs(const amx_ctx* ctx, size_t lds, int nt, int occ) {
   return (per_cu < 1 ? 1 : per_cu) * ctx->n_cus;
 }
 
+// One workgroup per tile, or a.streamk workgroups (f16x3 stream-K).  LDS: the tile's stage
+// buffers, or its RFF epilogue's staging pass (TL::RFF_ROWS x (BN + 4) floats) when that is larger.
 template <int EPI, class TL>
-int launch_nt(GemmArgs& a, hipStream_t stream) {
-  a.tiles_m = a.rows / TL::BM;
-  a.tiles_n = a.N / TL::BN;
-  const int nwg = a.tiles_m * a.tiles_n * a.groups;
-  if (nwg == 0) return AMX_OK;
-  constexpr size_t lds = (EPI == EPI_RFF && TL::LDS < rff_epi_lds(TL::BM, TL::BN)) ? rff_epi_lds(TL::BM, TL::BN) : TL::LDS;
-  hipLaunchKernelGGL((k_gemm_nt<EPI, TL>), dim3(nwg), dim3(TL::NT), lds, stream, a);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
-}
-
-template <int EPI, class TL>
-int launch_x6(GemmArgs& a, hipStream_t stream) {
-  a.tiles_m = a.rows / TL::BM;
-  a.tiles_n = a.N / TL::BN;
-  const int nwg = a.tiles_m * a.tiles_n * a.groups;
-  if (nwg == 0) return AMX_OK;
-  // the RFF epilogue stages the 128x(128+4) f32 tile through LDS (67.6 KB)
-  constexpr size_t lds = (EPI == EPI_RFF && TL::LDS < rff_epi_lds(TL::BM, TL::BN)) ? rff_epi_lds(TL::BM, TL::BN) : TL::LDS;
-  hipLaunchKernelGGL((k_gemm_x6<EPI, TL>), dim3(nwg), dim3(TL::NT), lds, stream, a);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
-}
-
-template <int EPI, class TL>
-int launch_h3(GemmArgs& a, hipStream_t stream) {
+int launch(void (*kernel)(GemmArgs), GemmArgs& a, hipStream_t stream) {
   a.tiles_m = a.rows / TL::BM;
   a.tiles_n = a.N / TL::BN;
   const int tiles = a.tiles_m * a.tiles_n * a.groups;
-  const int nwg = a.streamk ? a.streamk : tiles;  // stream-K: a.streamk workgroups
   if (tiles == 0) return AMX_OK;
-  // (the three-per-CU RFF tile stages its epilogue in two 64-row passes, the M16 tiles in
-  // passes of rff_m16_rows)
-  constexpr size_t rff_lds = TL::M16      ? rff_epi_lds(rff_m16_rows(TL::BM, TL::BN), TL::BN)
-                             : TL::OCC >= 3 ? rff_epi_lds(TL::BM / 2, TL::BN)
-                                            : rff_epi_lds(TL::BM, TL::BN);
+  constexpr size_t rff_lds = rff_epi_lds(TL::RFF_ROWS, TL::BN);
   constexpr size_t lds = (EPI == EPI_RFF && TL::LDS < rff_lds) ? rff_lds : TL::LDS;
-  hipLaunchKernelGGL((k_gemm_h3<EPI, TL>), dim3(nwg), dim3(TL::NT), lds, stream, a);
+  hipLaunchKernelGGL(kernel, dim3(a.streamk ? a.streamk : tiles), dim3(TL::NT), lds, stream, a);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
 }
+template <int EPI, class TL>
+int launch_nt(GemmArgs& a, hipStream_t stream) { return launch<EPI, TL>(k_gemm_nt<EPI, TL>, a, stream); }
+template <int EPI, class TL>
+int launch_x6(GemmArgs& a, hipStream_t stream) { return launch<EPI, TL>(k_gemm_x6<EPI, TL>, a, stream); }
+template <int EPI, class TL>
+int launch_h3(GemmArgs& a, hipStream_t stream) { return launch<EPI, TL>(k_gemm_h3<EPI, TL>, a, stream); }
 
-
-int check_common(const char* fn, int groups, int rows, int K, const float* A, int lda, const float* W,
-                 int ldw) {
+// the argument checks every GEMM entry point starts with (bk: the K granule of its path; W: the
+// fp32 weights or their limb image)
+int check_head(const char* fn, int groups, int rows, int K, int bk, const float* A, int lda, const void* W) {
   AMX_CHECK_ARG(groups >= 1 && groups <= AMX_MAX_MODELS, "%s: groups=%d", fn, groups);
   AMX_CHECK_ARG(rows >= 0 && rows % AMX_ROW_TILE == 0, "%s: rows=%d must be a multiple of %d", fn, rows,
                 AMX_ROW_TILE);
-  AMX_CHECK_ARG(K > 0 && K % BK == 0, "%s: K=%d must be a positive multiple of %d", fn, K, BK);
-  AMX_CHECK_ARG(A && W, "%s: null operand", fn);
-  AMX_CHECK_ARG(amx::aligned16(A) && amx::aligned16(W), "%s: operands must be 16-byte aligned", fn);
+  AMX_CHECK_ARG(K > 0 && K % bk == 0, "%s: K=%d must be a positive multiple of %d", fn, K, bk);
+  AMX_CHECK_ARG(A && W && amx::aligned16(A) && amx::aligned16(W), "%s: null/unaligned operand", fn);
   AMX_CHECK_ARG(lda >= K && lda % 4 == 0, "%s: lda=%d (K=%d) must be >= K and a multiple of 4", fn, lda, K);
+  return AMX_OK;
+}
+
+int check_common(const char* fn, int groups, int rows, int K, const float* A, int lda, const float* W,
+                 int ldw) {
+  if (int rc = check_head(fn, groups, rows, K, BK, A, lda, W)) return rc;
   AMX_CHECK_ARG(ldw >= K && ldw % 4 == 0, "%s: ldw=%d (K=%d) must be >= K and a multiple of 4", fn, ldw, K);
   return AMX_OK;
 }
 
 int check_x6(const char* fn, int groups, int rows, int K, const float* A, int lda, const uint16_t* W3,
              long long strideW3) {
-  AMX_CHECK_ARG(groups >= 1 && groups <= AMX_MAX_MODELS, "%s: groups=%d", fn, groups);
-  AMX_CHECK_ARG(rows >= 0 && rows % AMX_ROW_TILE == 0, "%s: rows=%d must be a multiple of %d", fn, rows,
-                AMX_ROW_TILE);
-  AMX_CHECK_ARG(K > 0 && K % XBK == 0, "%s: K=%d must be a positive multiple of %d", fn, K, XBK);
-  AMX_CHECK_ARG(A && W3 && amx::aligned16(A) && amx::aligned16(W3), "%s: null/unaligned operand", fn);
-  AMX_CHECK_ARG(lda >= K && lda % 4 == 0, "%s: lda=%d (K=%d) must be >= K and a multiple of 4", fn, lda, K);
+  if (int rc = check_head(fn, groups, rows, K, XBK, A, lda, W3)) return rc;
   AMX_CHECK_ARG(strideW3 % 8 == 0, "%s: strideW3=%lld must be a multiple of 8", fn, strideW3);
   return AMX_OK;
 }
 
 int check_h3(const char* fn, int groups, int rows, int K, const float* A, int lda, const uint16_t* W2,
              long long strideW2, const int* w_exp, const int* row_exp, int rexp_slots, int k_shared = 0) {
-  AMX_CHECK_ARG(groups >= 1 && groups <= AMX_MAX_MODELS, "%s: groups=%d", fn, groups);
-  AMX_CHECK_ARG(rows >= 0 && rows % AMX_ROW_TILE == 0, "%s: rows=%d must be a multiple of %d", fn, rows,
-                AMX_ROW_TILE);
-  AMX_CHECK_ARG(K > 0 && K % XBK == 0, "%s: K=%d must be a positive multiple of %d", fn, K, XBK);
-  AMX_CHECK_ARG(A && W2 && amx::aligned16(A) && amx::aligned16(W2), "%s: null/unaligned operand", fn);
-  AMX_CHECK_ARG(lda >= K && lda % 4 == 0, "%s: lda=%d (K=%d) must be >= K and a multiple of 4", fn, lda, K);
+  if (int rc = check_head(fn, groups, rows, K, XBK, A, lda, W2)) return rc;
   AMX_CHECK_ARG(strideW2 % 8 == 0, "%s: strideW2=%lld must be a multiple of 8", fn, strideW2);
   AMX_CHECK_ARG(w_exp && row_exp && rexp_slots >= 1, "%s: null exponents or rexp_slots=%d", fn, rexp_slots);
   AMX_CHECK_ARG(k_shared >= 0 && k_shared <= K && k_shared % 32 == 0,
@@ -1754,12 +1692,9 @@ extern "C" int amx_row_exponents(amx_ctx* ctx, int groups, int rows, int K, cons
 // covered), *nwg = G and *ksplit = ks.  (Rounds 3-6 used 128 x 256 tiles split at most 6 ways
 // here: 33.7 us per hidden layer at the sampler's 640 lanes, profiles/r06q_paths_trace_summary.txt
 // -- each workgroup ran a 10-K-tile chain and wrote a 128 KB partial tile.)
-#ifndef SMALL_KT
-#define SMALL_KT 7     // K-tiles per segment (target)
-#endif
-#ifndef SMALL_KSMAX
-#define SMALL_KSMAX 8  // segments per tile at most
-#endif
+constexpr int SMALL_KT = 7;     // K-tiles per segment (target; 7-14 equal, fewer slower:
+                                //   profiles/r06t_small_gemm_segments_ab.txt)
+constexpr int SMALL_KSMAX = 8;  // segments per tile at most
 static int small_plan(const amx_ctx* ctx, int groups, int rows, int N, int K, int bn, int* nwg, int* ksplit) {
   (void)ctx;
   if (rows <= 0 || rows % 128 != 0 || N % bn != 0 || K % 32 != 0 || groups < 1) return 0;
@@ -1806,7 +1741,7 @@ extern "C" int amx_gemm_bias_act_h3(amx_ctx* ctx, int groups, int rows, int N, i
   const hipStream_t s = (hipStream_t)stream;
   if (rows % 256 == 0 && N % 256 == 0 && K % 32 == 0 &&
       (long long)(rows / 256) * (N / 256) * groups >= resident_wgs(ctx, H256::LDS, H256::NT, 2))
-    return H3_W4 ? launch_h3<EPI_BIAS_ACT, H256w4>(a, s) : launch_h3<EPI_BIAS_ACT, H256>(a, s);
+    return launch_h3<EPI_BIAS_ACT, H256>(a, s);
   // one wave of row-block tiles: rows = RB * n_cus / (groups * N/256), RB in {128..224}
   if (N % 256 == 0 && K % 32 == 0) {
     const long long per = (long long)groups * (N / 256);
@@ -1894,9 +1829,7 @@ extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_
     a.N = 224;
     AMX_CHECK_ARG(strideW2 >= 2LL * K * 224 || groups == 1, "amx_gemm_out_unnorm_h3: strideW2=%lld", strideW2);
     if (K % 32 != 0) return launch_h3<EPI_UNNORM, H128x224k16>(a, s);
-#if OUT80
     if (rows % 80 == 0 && (long long)groups * (rows / 80) == ctx->n_cus) return launch_h3<EPI_UNNORM, H80x224>(a, s);
-#endif
     // lane counts whose 128 x 224 tiles (14 waves) are fewer than the CUs (4096-7168 lanes x 4
     // members: 128-224 tiles): stream-K over one workgroup per CU (each tile's K range in <= 3
     // segments), instead of the row-block tiles' 4-7 waves per workgroup
@@ -1966,9 +1899,7 @@ extern "C" int amx_rff_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, i
       return launch_h3<EPI_RFF, H160x256r>(a, (hipStream_t)stream);
     // (at 40 960 rows the 128 x 128 tile is faster: 121 vs 145 us under the profiler)
     if ((rows / 128) * (F / 128) < ctx->n_cus && F % 64 == 0) return launch_h3<EPI_RFF, H128x64k32>(a, (hipStream_t)stream);
-#if RFF_OCC3
     if ((long long)(rows / 128) * (F / 128) > 2LL * ctx->n_cus) return launch_h3<EPI_RFF, H128rff3>(a, (hipStream_t)stream);
-#endif
     return launch_h3<EPI_RFF, H128k32>(a, (hipStream_t)stream);
   }
   return launch_h3<EPI_RFF, H128>(a, (hipStream_t)stream);

@@ -1,6 +1,6 @@
 // Internal building blocks of the GEMM launches (amx_gemm.hip): vector types, GemmArgs, the
-// XCD-aware tile map, and the f16x3 tile family (fp32 as two scaled fp16 limbs, three MFMA
-// products).
+// XCD-aware tile map, and the two f16x3 tile families (fp32 as two scaled fp16 limbs, three MFMA
+// products) with the pieces their tile loops share.
 #pragma once
 
 #include "amx_common.h"
@@ -41,7 +41,7 @@ struct GemmArgs {
   int k_shared;            // leading K columns of A read from group 0's rows for every group
                            //   (the ensemble's x0 slice, assembled once; multiple of the tile's BK)
   int ksplit;              // partial-tile slots per tile in split_scratch (stream-K output layer)
-  int streamk;             // > 0: stream-K over this many workgroups (LATE M16 UNNORM tiles)
+  int streamk;             // > 0: stream-K over this many workgroups (16x16x32 tiles)
   float* split_scratch;    //   raw partial tiles [tile][slot][MB][NB][NT] f32x4 (amx_set_split_workspace)
   uint32_t* split_cnt;     //   arrivals per tile (zero between launches: the last arriver resets it)
   uint64_t* timer;         // amx_set_gemm_timer buffer (null: off)
@@ -107,53 +107,65 @@ __device__ __forceinline__ int exp_of_bits(uint32_t absbits) {
   return e > 100 ? 100 : e;
 }
 
-// NSUB 16-k granules per K-tile (BK = 16 NSUB); LDS row = NSUB x [limb0 16 | limb1 16] + 8 pad
-// (20 dwords at NSUB 1, 36 at NSUB 2: the 16 rows of a ds_read_b128 lane group land on
-// distinct 4-bank slots)
-template <int WM_, int WN_, int TM_, int TN_, int OCC_ = 2, int NSUB_ = 1, bool LATE_ = false, bool AMAP_ = true,
-          bool M16_ = false, int MB16_ = 0, int NB16_ = 0, bool PIN_ = false, bool EARLY_ = false,
-          bool SPLIT_ = false, bool DEEPA_ = false, bool SPREAD_ = false>
+// LDS of the RFF epilogue: a staged rows x (BN + 4) f32 tile
+constexpr size_t rff_epi_lds(int rows, int bn) { return (size_t)rows * (bn + 4) * 4; }
+
+// 32x32x16 form (v_mfma_f32_32x32x16_f16): WM x WN waves of TM x TN blocks of 32x32, NSUB 16-k
+// granules per K-tile (BK = 16 NSUB), plain double buffer (one barrier per K-tile, the next
+// tile's loads issued ahead of the MFMA block).  LDS row = NSUB x [limb0 16 | limb1 16] + 8 pad
+// (20 dwords at NSUB 1, 36 at NSUB 2: the 16 rows of a ds_read_b128 lane group land on distinct
+// 4-bank slots); the row exponents sit behind the two stage buffers.
+// A-map (BK 32): the 16 lanes of a ds_write_b64 group stage rows r and r+2 (36-dword rows:
+// 72 = 8 mod 32 banks apart, so their 2 x 8 dwords interleave) instead of r and r+1 (2-way
+// bank conflict on every A limb store): 2% per layer (profiles/r01_h3_variants.txt)
+template <int WM_, int WN_, int TM_, int TN_, int OCC_ = 2, int NSUB_ = 1>
 struct TileH3 {
-  static constexpr bool EARLY = EARLY_ && M16_ && LATE_;  // first fragment reads before the publish
-  // SPLIT: the publish of tile t+1 and the loads of t+2 are cut into one piece per m-block and
-  // placed behind that block's MFMAs (the guide's split write-after-barrier schedule)
-  static constexpr bool SPLIT = SPLIT_ && EARLY;
-  // DEEPA (SPLIT): the A operand's loads run two K-tiles ahead of its publish instead of one (two
-  // register sets; the loop unrolled by two): the output layer's A panel is streamed from HBM
-  // once (N = 224 columns per A row), so its K loop waits on load latency, not on the MFMAs
-  static constexpr bool DEEPA = DEEPA_ && SPLIT;
-  // SPREAD (SPLIT): the staging pieces dealt evenly over the m-blocks (ceil(pieces / MB) behind
-  // each) instead of one per block with the rest behind the last
-  static constexpr bool SPREAD = SPREAD_ && SPLIT;
-  // PIN: sched_barriers keep each block's fragment reads one MFMA group ahead of their use
-  static constexpr bool PIN = PIN_;
+  static constexpr bool M16 = false;
   static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, OCC = OCC_, NSUB = NSUB_, BK = 16 * NSUB_;
-  // M16: v_mfma_f32_16x16x32_f16 on 16x16 blocks (BK 32; 4 fp32 accumulators per lane and
-  // block) instead of 32x32x16 -- the same cycles per FLOP at lower power per FLOP
-  // (MI355X_MICROARCH.md); LDS rows of 40 dwords (conflict-free for its lane->k map and for
-  // the plain A staging map), the row exponents live in the stage area (160 KB LDS)
-  static constexpr bool M16 = M16_;
-  static_assert(!M16 || NSUB == 2, "the 16x16x32 MFMA consumes a 32-deep K-tile");
-  // AMAP (BK 32): the 16 lanes of a ds_write_b64 group stage rows r and r+2 (36-dword rows:
-  // 72 = 8 mod 32 banks apart, so their 2 x 8 dwords interleave) instead of r and r+1 (2-way
-  // bank conflict on every A limb store): 2% per layer (tools/h3_variants.py)
-  static constexpr bool AMAP = AMAP_ && !M16_;
-  // LATE: barrier -> publish tile t+1 -> issue the loads of t+2 -> compute t (write after
-  // the barrier: the LDS writes drain under the MFMAs, the loads get a whole K-tile)
-  static constexpr bool LATE = LATE_;
-  static constexpr int LD = NSUB * 32 + (M16 ? 16 : 8);       // f16 per LDS row
+  static constexpr int LD = NSUB * 32 + 8;                     // f16 per LDS row
   static constexpr int NT = WM * WN * 64;
-  // M16: MB x NB blocks of 16x16 per wave (default 2TM x 2TN; MB16_/NB16_ override, e.g. 7
-  // column blocks = 112 columns); 32x32 form: TM x TN blocks of 32x32
-  static constexpr int MB = (M16 && MB16_) ? MB16_ : 2 * TM, NB = (M16 && NB16_) ? NB16_ : 2 * TN;
-  static constexpr int WROWS = M16 ? MB * 16 : TM * 32, WCOLS = M16 ? NB * 16 : TN * 32;
-  static constexpr int BM = WM * WROWS, BN = WN * WCOLS;
+  static constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   static constexpr int STAGE = (BM + BN) * LD;                 // f16 of one stage (A + W)
-  static constexpr size_t LDS = 2 * STAGE * sizeof(uint16_t) + (M16 ? 0 : BM * sizeof(int));
-  static constexpr int SEXP = M16 ? STAGE : 2 * STAGE;         // f16 offset of the row exponents
+  static constexpr size_t LDS = 2 * STAGE * sizeof(uint16_t) + BM * sizeof(int);
+  static constexpr int SEXP = 2 * STAGE;                       // f16 offset of the row exponents
   static constexpr int CPR = 4 * NSUB;                         // 16-B chunks per row and K-tile (A f32 and W)
   static constexpr int NA = BM * CPR, NW = BN * CPR;
   static constexpr int VA = (NA + NT - 1) / NT, VW = (NW + NT - 1) / NT;
+  // rows of the RFF epilogue's staging pass (at three workgroups per CU: two 64-row passes)
+  static constexpr int RFF_ROWS = OCC >= 3 ? BM / 2 : BM;
+  static_assert(LDS <= 160 * 1024, "LDS");
+};
+
+// 16x16x32 form (v_mfma_f32_16x16x32_f16 on 16x16 blocks, BK 32; 4 fp32 accumulators per lane
+// and block): the same cycles per FLOP as 32x32x16 at lower power per FLOP
+// (MI355X_MICROARCH.md).  WM x WN waves of MB x NB blocks.  LDS rows of 40 dwords
+// (conflict-free for its lane->k map and for the plain A staging map); the row exponents live
+// in the stage area (160 KB LDS).
+// Schedule (the guide's split write-after-barrier): barrier -> the first fragment reads of tile
+// t -> per m-block, its MFMAs with the fragment reads of the next block pinned one MFMA group
+// ahead (sched_barrier), then one piece of tile t+1's publish and of tile t+2's loads -- the LDS
+// writes drain under the MFMAs, the loads get a whole K-tile.
+// DEEPA: the A operand's loads run two K-tiles ahead of its publish instead of one (two register
+// sets; the loop unrolled by two): the output layer's A panel is streamed from HBM once (N = 224
+// columns per A row), so its K loop waits on load latency, not on the MFMAs
+template <int WM_, int WN_, int MB_, int NB_, int OCC_ = 2, bool DEEPA_ = false>
+struct TileH3M16 {
+  static constexpr bool M16 = true, DEEPA = DEEPA_;
+  static constexpr int WM = WM_, WN = WN_, MB = MB_, NB = NB_, OCC = OCC_, BK = 32;
+  static constexpr int LD = 64 + 16;                           // f16 per LDS row
+  static constexpr int NT = WM * WN * 64;
+  static constexpr int WROWS = MB * 16, WCOLS = NB * 16;
+  static constexpr int BM = WM * WROWS, BN = WN * WCOLS;
+  static constexpr int STAGE = (BM + BN) * LD;                 // f16 of one stage (A + W)
+  static constexpr size_t LDS = 2 * STAGE * sizeof(uint16_t);
+  static constexpr int SEXP = STAGE;                           // f16 offset of the row exponents
+  static constexpr int CPR = 8;                                // 16-B chunks per row and K-tile (A f32 and W)
+  static constexpr int NA = BM * CPR, NW = BN * CPR;
+  static constexpr int VA = (NA + NT - 1) / NT, VW = (NW + NT - 1) / NT;
+  // rows of the RFF epilogue's staging pass: the whole tile when its [BM][BN + 4] floats fit
+  // 80 KB, else the largest multiple of 32 rows that does (the 160 x 256 tile: 64 rows)
+  static constexpr int RFF_ROWS =
+      rff_epi_lds(BM, BN) <= 80 * 1024 ? BM : (int)((80 * 1024) / ((size_t)(BN + 4) * 4 * 32)) * 32;
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
