@@ -5,8 +5,8 @@ cost with the ensemble-disagreement bonus, the AMP/GAIL least-squares discrimina
 reward and the humanoid3d fall/horizon termination, as hand-written HIP kernels for
 gfx950 behind a C ABI (include/amx_hip.h, libamx_hip.so) and the reference's Python
 surfaces (SimEnv, sample_points, RBFLinearCost, GAILCost, DynamicsEnsemble), plus the
-sampler's consumers: returns, MLP value baseline and GAE (mjrl process_samples) and the
-NPG policy update (mjrl npg_cg).
+sampler's consumers: returns, MLP value baseline (prediction and the mini-batch Adam fit) and
+GAE (mjrl process_samples, MLPBaseline) and the NPG policy update (mjrl npg_cg).
 
 The native library is loaded on first use; there is no CPU fallback.
 """

@@ -136,7 +136,11 @@ SIGNATURES = {
     "amx_value_head": (c_int, [vp, c_int, vp, c_int, c_int, vp, vp, vp, vp]),
     "amx_gae": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, vp, vp, c_ll, vp, c_dbl, c_dbl, vp, vp, vp]),
     "amx_adv_whiten": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, c_dbl, vp, vp, vp]),
-    "amx_philox": (c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
+    "amx_vfit_work": (c_ll, [c_int, c_int, c_int]),
+    "amx_vfit_param_count": (c_ll, [c_int, c_int, c_int]),
+    "amx_vfit_epoch": (c_int, [vp, c_int, vp, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                               c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, vp, vp, vp]),
+    "amx_philox":(c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
     "amx_mt_seed": (c_int, [vp, c_int, vp, vp, c_int]),
     "amx_mt_policy_noise": (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_ll, c_ll]),
 }

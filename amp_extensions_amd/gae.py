@@ -9,8 +9,11 @@ Two layouts share the same kernels (include/amx_hip.h, "segment grid"):
     `process_samples.compute_returns` + `compute_advantages` (mjrl/mjrl/utils/process_samples.py).
 The value MLP is the reference's MLPBaseline (mjrl/mjrl/baselines/mlp_baseline.py:10-108):
 features [clip(obs,-10,10)/10, (t/1000)^1..4] -> Linear/ReLU ... -> Linear(., 1), run on the
-MFMA GEMM with the hidden widths zero-padded to 128.  Fitting the baseline (Adam) belongs to
-the learner and stays with the caller's torch model; call `sync_from` after each fit.
+MFMA GEMM with the hidden widths zero-padded to 128.  Fitting the baseline
+(MLPBaseline.fit, mlp_baseline.py:61-97: mini-batch Adam through fit_data,
+mjrl/mjrl/utils/optimize_model.py:7-36) runs on the device too (`fit`, `fit_grid`,
+csrc/amx_vfit.hip) on the same feature rows; the weights and the Adam state live in device
+memory, and `sync_to` writes both into an mjrl baseline where a checkpoint is taken.
 """
 from __future__ import annotations
 
@@ -33,35 +36,74 @@ def init_mlp_baseline_params(inp_dim: int, hidden=(128, 128), seed: int | None =
     return [(l.weight.data.clone(), l.bias.data.clone()) for l in layers]
 
 
-class DeviceMLPBaseline:
-    """MLPBaseline.predict on the device.  Workspace rows: [feat kf | h0 | h1 | ...] with
-    kf = round_up(S+4, 32) and every hidden width padded to a multiple of 128."""
+FIT_BATCH = 64    # mini-batch rows of the device fit
+FIT_HIDDEN = 128  # widest hidden layer of the device fit
 
-    def __init__(self, ctx: AmxContext, layers):
+
+class DeviceMLPBaseline:
+    """MLPBaseline.predict and MLPBaseline.fit on the device.  Workspace rows:
+    [feat kf | h0 | h1 | ...] with kf = round_up(S+4, 32) and every hidden width padded to a
+    multiple of 128.
+
+    `learn_rate`, `reg_coef`, `batch_size`, `epochs` are MLPBaseline's constructor arguments
+    (same defaults); `betas` / `eps` are torch.optim.Adam's.  The fit supports two hidden
+    layers of width <= 128 and batch_size 64 (run.py's critic and MLPBaseline's default);
+    `fit` raises NotImplementedError for anything else, prediction is not restricted.
+
+    Single rank only: the fit runs over the rows this process holds.  With lanes sharded over
+    ranks a global fit (every rank stepping the same weights over all ranks' rows) needs a
+    design of its own and is not provided."""
+
+    def __init__(self, ctx: AmxContext, layers, *, learn_rate: float = 1e-3, reg_coef: float = 0.0,
+                 batch_size: int = 64, epochs: int = 1, betas=(0.9, 0.999), eps: float = 1e-8):
         self.ctx = ctx
         self.kf = round_up(ctx.S + 4, 32)
         self._ws = None
+        self.learn_rate, self.reg_coef = float(learn_rate), float(reg_coef)
+        self.batch_size, self.epochs = int(batch_size), int(epochs)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self._adam = None  # (m, v, step) device tensors, allocated by the first fit / optimizer load
+        self._fit_work = None
         self.sync_from(layers)
 
     @classmethod
     def from_mjrl(cls, ctx: AmxContext, baseline):
-        """Build from an mjrl `MLPBaseline` (its nn.Sequential of Linear/ReLU)."""
-        return cls(ctx, cls._layers_of(baseline))
+        """Build from an mjrl `MLPBaseline`: its nn.Sequential of Linear/ReLU, batch_size and
+        epochs, and its optimizer's hyper-parameters and state (step, exp_avg, exp_avg_sq;
+        absent before the optimizer's first step)."""
+        g = baseline.optimizer.param_groups[0]
+        if g.get("amsgrad", False):
+            raise NotImplementedError("the device fit implements Adam without amsgrad")
+        self = cls(ctx, cls._layers_of(baseline), learn_rate=g["lr"], reg_coef=g["weight_decay"],
+                   batch_size=baseline.batch_size, epochs=baseline.epochs, betas=g["betas"], eps=g["eps"])
+        if self.fit_supported():  # a shape the fit refuses still predicts; it has no state to load
+            self.load_optimizer(baseline.optimizer)
+        return self
 
     @staticmethod
     def _layers_of(baseline):
         return [(m.weight.data, m.bias.data) for m in baseline.model if isinstance(m, nn.Linear)]
 
-    def sync_from(self, layers) -> None:
-        """Upload (W [out, in], b) per layer; accepts the list or an mjrl MLPBaseline."""
+    def sync_from(self, layers, optimizer=None) -> None:
+        """Upload (W [out, in], b) per layer; accepts the list or an mjrl MLPBaseline.  The
+        Adam state is left alone unless `optimizer` (the torch.optim.Adam over the same
+        parameters, in layer order) is given."""
         if hasattr(layers, "model"):
             layers = self._layers_of(layers)
+        self._sync_weights(layers)
+        if optimizer is not None:
+            self.load_optimizer(optimizer)
+
+    def _sync_weights(self, layers) -> None:
         c, dev = self.ctx, self.ctx.device
         if len(layers) < 2:
             raise ValueError("MLPBaseline needs at least one hidden layer")
         if layers[0][0].shape[1] != c.S + 4 or layers[-1][0].shape[0] != 1:
             raise ValueError(f"baseline layers must map {c.S + 4} features to 1 value")
         widths = [int(W.shape[0]) for W, _ in layers[:-1]]
+        if self._adam is not None and widths != self.widths:
+            self._adam = None  # another model: its moments do not carry over
+        self.widths = widths
         self.Hp = [round_up(h, 128) for h in widths]
         self.col = [0, self.kf]
         for hp in self.Hp:
@@ -94,11 +136,22 @@ class DeviceMLPBaseline:
                      lengths: torch.Tensor | None = None, t0: torch.Tensor | None = None,
                      base: torch.Tensor | None = None) -> torch.Tensor:
         """Baseline values of every grid row (rows = row-space size) -> f32 [rows_pad]."""
+        self._features(rows, T, L, obs, ldo, end, stride, lengths, t0, base)
+        return self._forward(rows)
+
+    def _features(self, rows, T, L, obs, ldo, end, stride, lengths, t0, base) -> torch.Tensor:
+        """MLPBaseline._features of every grid row into the workspace's first kf columns."""
+        c = self.ctx
+        ws = self.workspace(rows)
+        N.check(c.lib.amx_value_features(c.h, T, L, _ptr(lengths), _ptr(t0), _ptr(base), stride, end.data_ptr(),
+                                         obs.data_ptr(), ldo, ws.data_ptr(), self.ldv, c.stream), "amx_value_features")
+        return ws
+
+    def _forward(self, rows: int) -> torch.Tensor:
+        """The model over the workspace's feature rows -> f32 [rows_pad]."""
         c = self.ctx
         ws = self.workspace(rows)
         rp = round_up(rows, 128)
-        N.check(c.lib.amx_value_features(c.h, T, L, _ptr(lengths), _ptr(t0), _ptr(base), stride, end.data_ptr(),
-                                         obs.data_ptr(), ldo, ws.data_ptr(), self.ldv, c.stream), "amx_value_features")
         for i in range(len(self.Hp)):
             K = self.kf if i == 0 else self.Hp[i - 1]
             A = ws[:, self.col[i]:]
@@ -109,6 +162,187 @@ class DeviceMLPBaseline:
         N.check(c.lib.amx_value_head(c.h, rp, h.data_ptr(), self.ldv, self.Hp[-1], self.w_head.data_ptr(),
                                      self.b_head.data_ptr(), self._v.data_ptr(), c.stream), "amx_value_head")
         return self._v[:rp]
+
+    # ---- fit ---------------------------------------------------------------------------------
+
+    def fit_supported(self) -> bool:
+        return len(self.widths) == 2 and max(self.widths) <= FIT_HIDDEN and self.batch_size == FIT_BATCH
+
+    def _check_fit_supported(self) -> None:
+        if len(self.widths) != 2 or max(self.widths) > FIT_HIDDEN:
+            raise NotImplementedError(f"the device fit supports two hidden layers of width <= {FIT_HIDDEN} "
+                                      f"(MLPBaseline's default critic), not {tuple(self.widths)}")
+        if self.batch_size != FIT_BATCH:
+            raise NotImplementedError(f"the device fit supports batch_size {FIT_BATCH}, not {self.batch_size}")
+
+    def _param_slices(self):
+        """(offset, padded shape, live shape) of W0, b0, W1, b1, w2, b2 in the Adam moment vectors
+        (amx_vfit_param_count's layout), in torch's parameter order."""
+        k, (h0, h1), (p0, p1) = self.ctx.S + 4, self.widths, self.Hp
+        shapes = [((p0, self.kf), (h0, k)), ((p0,), (h0,)), ((p1, p0), (h1, h0)), ((p1,), (h1,)),
+                  ((1, p1), (1, h1)), ((1,), (1,))]
+        out, o = [], 0
+        for pad, live in shapes:
+            out.append((o, pad, live))
+            o += int(np.prod(pad))
+        return out, o
+
+    def _adam_state(self):
+        if self._adam is None:
+            _, P = self._param_slices()
+            assert P == self.ctx.lib.amx_vfit_param_count(self.kf, self.Hp[0], self.Hp[1])
+            dev = self.ctx.device
+            self._adam = (torch.zeros(P, dtype=torch.float32, device=dev),
+                          torch.zeros(P, dtype=torch.float32, device=dev),
+                          torch.zeros(1, dtype=torch.int64, device=dev))
+        return self._adam
+
+    def load_optimizer(self, optimizer) -> None:
+        """Adam state of a torch.optim.Adam over the model's parameters (layer order: weight,
+        bias per Linear) -> the device moments and step count.  Parameters without state (no
+        step taken yet) load as zeros."""
+        self._check_fit_supported()
+        params = optimizer.param_groups[0]["params"]
+        slices, P = self._param_slices()
+        if len(params) != len(slices):
+            raise ValueError(f"optimizer holds {len(params)} parameters, the baseline has {len(slices)}")
+        m, v, step = torch.zeros(P), torch.zeros(P), 0
+        for p, (o, pad, live) in zip(params, slices):
+            st = optimizer.state.get(p, {})
+            if not st:
+                continue
+            if tuple(st["exp_avg"].shape) != live:
+                raise ValueError(f"optimizer state of shape {tuple(st['exp_avg'].shape)}, expected {live}")
+            step = int(st["step"])
+            idx = tuple(slice(0, n) for n in live)
+            m[o:o + int(np.prod(pad))].view(pad)[idx] = st["exp_avg"].detach().float().cpu()
+            v[o:o + int(np.prod(pad))].view(pad)[idx] = st["exp_avg_sq"].detach().float().cpu()
+        dm, dv, dstep = self._adam_state()
+        dm.copy_(m)
+        dv.copy_(v)
+        dstep.fill_(step)
+
+    def adam_state(self):
+        """(step, [exp_avg per parameter], [exp_avg_sq per parameter]) on the host, in torch's
+        parameter order and live (unpadded) shapes."""
+        self._check_fit_supported()
+        dm, dv, dstep = self._adam_state()
+        m, v = dm.cpu(), dv.cpu()
+        slices, _ = self._param_slices()
+        cut = lambda x: [x[o:o + int(np.prod(pad))].view(pad)[tuple(slice(0, n) for n in live)].clone()
+                         for o, pad, live in slices]
+        return int(dstep.item()), cut(m), cut(v)
+
+    def layers(self):
+        """[(W [out, in], b)] per layer on the host, live shapes (the inverse of sync_from)."""
+        k_in, out = self.ctx.S + 4, []
+        for W, b, h in zip(self.W, self.b, self.widths):
+            out.append((W[:h, :k_in].cpu().clone(), b[:h].cpu().clone()))
+            k_in = h
+        out.append((self.w_head[:k_in].cpu().reshape(1, -1).clone(), self.b_head.cpu().clone()))
+        return out
+
+    def sync_to(self, baseline) -> None:
+        """Write the weights into `baseline.model` and the Adam state into `baseline.optimizer`
+        (an mjrl MLPBaseline or anything with those two attributes), so that
+        model.state_dict() / optimizer.state_dict() checkpoint what the device holds and a host
+        fit continues where the device stopped."""
+        lin = [m for m in baseline.model if isinstance(m, nn.Linear)]
+        mine = self.layers()
+        if [tuple(l.weight.shape) for l in lin] != [tuple(W.shape) for W, _ in mine]:
+            raise ValueError("baseline.model's layers do not match the device baseline")
+        with torch.no_grad():
+            for l, (W, b) in zip(lin, mine):
+                l.weight.copy_(W)
+                l.bias.copy_(b)
+        if self._adam is None:
+            return
+        step, ms, vs = self.adam_state()
+        opt = baseline.optimizer
+        for p, m, v in zip(opt.param_groups[0]["params"], ms, vs):
+            if step == 0:
+                opt.state.pop(p, None)
+            else:
+                opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.to(p.device).view_as(p),
+                                "exp_avg_sq": v.to(p.device).view_as(p)}
+
+    def fit_grid(self, rows: int, T: int, L: int, obs: torch.Tensor, ldo: int, end: torch.Tensor, stride: int,
+                 returns: torch.Tensor, lengths: torch.Tensor | None = None, t0: torch.Tensor | None = None,
+                 base: torch.Tensor | None = None, *, perms=None, return_errors: bool = False,
+                 return_all_errors: bool = False):
+        """MLPBaseline.fit over grid rows already on the device: `predict_grid`'s arguments plus
+        `returns` (f32 or f64, one per row of the row space; cast to f32 on the device like the
+        reference's returns.astype('float32')).  Every one of the `rows` rows must belong to the
+        grid (engine buffers and concatenated paths do).  `epochs` epochs of int(rows / 64) - 1
+        Adam steps each; epoch e batches rows through perms[e] (int array of `rows` indices) or,
+        by default, np.random.permutation(rows) from numpy's global RNG, exactly as fit_data
+        draws it.  Returns what MLPBaseline.fit returns."""
+        self._check_fit_supported()
+        if rows < 2 * self.batch_size:
+            raise ValueError(f"fit needs at least {2 * self.batch_size} rows (int(rows / batch_size) - 1 steps), "
+                             f"got {rows}")
+        c, dev = self.ctx, self.ctx.device
+        used = (rows // self.batch_size - 1) * self.batch_size  # rows the steps of an epoch read
+        host_perms = []
+        for ep in range(self.epochs):
+            p = np.random.permutation(rows) if perms is None else np.asarray(perms[ep])
+            if p.ndim != 1 or p.shape[0] < used or p.min() < 0 or p.max() >= rows:
+                raise ValueError(f"perms[{ep}] must hold at least {used} row indices in [0, {rows})")
+            host_perms.append(p.astype(np.int32))
+        y = returns.reshape(-1)[:rows].to(torch.float32).contiguous()
+        ws = self._features(rows, T, L, obs, ldo, end, stride, lengths, t0, base)
+
+        def error():  # sum((returns - pred)^2) / (sum(returns^2) + 1e-8), mlp_baseline.py:82-83
+            e = y - self._forward(rows)[:rows]
+            return (torch.sum(e * e) / (torch.sum(y * y) + 1e-8)).cpu().numpy()[()]
+
+        error_before = error() if return_errors else None
+        m, v, step = self._adam_state()
+        if self._fit_work is None:
+            self._fit_work = torch.zeros(c.lib.amx_vfit_work(self.kf, self.Hp[0], self.Hp[1]) // 4,
+                                         dtype=torch.float32, device=dev)
+        losses = torch.zeros(max(self.epochs, 1), dtype=torch.float32, device=dev)
+        for ep, p in enumerate(host_perms):
+            perm_d = torch.from_numpy(p).to(dev)
+            N.check(c.lib.amx_vfit_epoch(c.h, rows, ws.data_ptr(), self.ldv, y.data_ptr(), perm_d.data_ptr(), self.kf,
+                                         self.Hp[0], self.Hp[1], self.W[0].data_ptr(), self.b[0].data_ptr(),
+                                         self.W[1].data_ptr(), self.b[1].data_ptr(), self.w_head.data_ptr(),
+                                         self.b_head.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(),
+                                         self.learn_rate, self.betas[0], self.betas[1], self.eps, self.reg_coef,
+                                         self._fit_work.data_ptr(), losses[ep:].data_ptr(), c.stream),
+                    "amx_vfit_epoch")
+        epoch_losses = [l.reshape(1) for l in losses[:self.epochs].cpu().numpy()]
+        if return_errors:
+            error_after = error()
+            if return_all_errors:
+                return error_before, error_after, epoch_losses
+            return error_before, error_after
+        return None
+
+    def fit(self, paths, return_errors: bool = False, return_all_errors: bool = False, perms=None):
+        """MLPBaseline.fit(paths, return_errors, return_all_errors) (mlp_baseline.py:61-97) on
+        the device: `paths` are mjrl path dicts with "observations" and "returns"; returns
+        (error_before, error_after[, epoch_losses]) like the reference when return_errors is
+        set, else None.  The permutations come from numpy's global RNG as in fit_data (a caller
+        who seeds numpy gets the reference's batches) unless `perms` injects one per epoch."""
+        self._check_fit_supported()
+        c, dev = self.ctx, self.ctx.device
+        lens = np.array([len(p["observations"]) for p in paths], dtype=np.int64)
+        n_rows = int(lens.sum())
+        if n_rows < 2 * self.batch_size:
+            raise ValueError(f"fit needs at least {2 * self.batch_size} rows (int(rows / batch_size) - 1 steps), "
+                             f"got {n_rows}")
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        obs = torch.from_numpy(np.ascontiguousarray(np.concatenate([p["observations"] for p in paths]),
+                                                    dtype=np.float64).reshape(n_rows, -1)).to(dev)
+        ret = torch.from_numpy(np.concatenate([np.asarray(p["returns"]).reshape(-1) for p in paths])
+                               .astype(np.float32)).to(dev)
+        end = np.zeros(n_rows, dtype=np.uint8)
+        end[(offs + lens - 1)[lens > 0]] = 1
+        return self.fit_grid(n_rows, int(lens.max(initial=0)), len(paths), obs, c.S, torch.from_numpy(end).to(dev), 1,
+                             ret, lengths=torch.from_numpy(lens.astype(np.int32)).to(dev),
+                             base=torch.from_numpy(offs).to(dev), perms=perms, return_errors=return_errors,
+                             return_all_errors=return_all_errors)
 
 
 def _ptr(t):

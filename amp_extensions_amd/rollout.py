@@ -683,6 +683,21 @@ class RolloutEngine:
                                                                        out=torch.empty_like(adv))
         return out
 
+    def fit_baseline(self, baseline, returns: torch.Tensor, **kw):
+        """MLPBaseline.fit over the recorded steps (batch_reinforce.py:190's
+        `self.baseline.fit(paths, ...)`) without the rows leaving the device: `returns` is
+        `advantages()["returns"]` ([T, B], f64 or f32); the rows, their order (row t * B + lane)
+        and the in-trajectory positions are the ones `advantages()` gives the baseline.
+        Keywords and return values are `DeviceMLPBaseline.fit_grid`'s.  Single rank only: with
+        lanes sharded over ranks this fits each rank's own rows."""
+        c, T, B = self.ctx, self.t, self.B
+        rows = T * B
+        if returns.numel() != rows:
+            raise ValueError(f"returns holds {returns.numel()} values, the buffers {rows} rows")
+        obs = self.obs[:T].reshape(rows, c.S)
+        end = self.done[:T].reshape(rows)
+        return baseline.fit_grid(rows, T, B, obs, c.S, end, B, returns, t0=self.steps0, **kw)
+
     def bonus_mmd(self, allreduce=None) -> float:
         """infos['bonus_mmd'] = mean(-rewards) - expert cost (batch_reinforce.py:169).
         `allreduce` (lanes sharded over ranks, as for relabel): the mean over every rank's

@@ -660,6 +660,40 @@ int amx_adv_whiten(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t
                    long long stride, const double* adv, double eps, double* out, double* stats,
                    void* stream);
 
+/* ---- fitting the value baseline (MLPBaseline.fit) ------------------------------ */
+
+/* The fit supports the (S+4) -> H0 -> H1 -> 1 ReLU MLP with both hidden widths <= 128
+ * (padded: H0p = H1p = 128; kf = round_up(S + 4, 32)) and mini-batches of 64 rows.
+ * amx_vfit_work: bytes of the opaque fit workspace (the gathered batch, activations, their
+ * gradients, the W1 gradient, the loss sum and the step's Adam constants); amx_vfit_param_count: floats of each
+ * Adam moment vector, laid out W0 [H0p, kf] | b0 [H0p] | W1 [H1p, H0p] | b1 [H1p] |
+ * w2 [H1p] | b2 [1].  Pure host arithmetic; -1 (and amx_last_error) for another shape. */
+long long amx_vfit_work(int kf, int H0p, int H1p);
+long long amx_vfit_param_count(int kf, int H0p, int H1p);
+
+/* One epoch of mjrl's fit_data (mjrl/mjrl/utils/optimize_model.py:21-35) as
+ * MLPBaseline.fit calls it (mjrl/mjrl/baselines/mlp_baseline.py:85): num_steps =
+ * n_rows / 64 - 1 mini-batch steps; step mb takes rows perm[64 mb .. 64 mb + 63] of feat
+ * [n_rows, ldf] (what amx_value_features writes) and of returns (f32), runs the forward
+ * h0 = relu(x W0^T + b0), h1 = relu(h0 W1^T + b1), y^ = h1 . w2 + b2, loss = mean((y^ - y)^2),
+ * autograd's backward (dy = 2 (y^ - y) / 64, ReLU mask "output > 0") and torch.optim.Adam
+ * (no amsgrad; weight_decay added to every gradient, biases included):
+ *   g += wd w;  m += (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g g;
+ *   w -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),
+ * t = ++adam_step[0] (device memory, persists across epochs and fits like the reference's
+ * optimizer; beta^t formed in double).  adam_m / adam_v: amx_vfit_param_count floats each,
+ * zero before the first step.  Weights use DeviceMLPBaseline's padded layout (W0 [128, kf],
+ * W1 [128, 128] row-major, zero padding); padded entries and their moments stay exactly 0.
+ * All arithmetic is fp32, in a fixed order.  epoch_loss[0] (device) = sum of the step
+ * losses / num_steps.  Rows past 64 (num_steps) of perm are not used; perm entries must lie
+ * in [0, n_rows) (the kernels clamp).  A step is four launches on `stream`; nothing in them
+ * waits on another workgroup.  One fit at a time per workspace. */
+int amx_vfit_epoch(amx_ctx* ctx, int n_rows, const float* feat, int ldf, const float* returns,
+                   const int32_t* perm, int kf, int H0p, int H1p, float* W0, float* b0, float* W1,
+                   float* b1, float* w2, float* b2, float* adam_m, float* adam_v,
+                   long long* adam_step, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, void* work, float* epoch_loss, void* stream);
+
 /* ---- RNG ----------------------------------------------------------------------- */
 
 /* Philox4x32-10 block for (key = seed, counter = {ctr0, ctr1, ctr2, ctr3}), written
