@@ -222,6 +222,16 @@ class RolloutEngine:
         self.t = 0
         self._scored = 0
 
+    def sync_step_counter(self, to_device: bool = False) -> None:
+        """The host policy counter as of now: graph replays advance dev_step only, so after one
+        the device counter is read back (a host sync).  to_device: dev_step is then set to the
+        host counter (eager steps advance the host's only), as a capture expects it."""
+        if self._graph_ahead:
+            self.step_counter = int(self.dev_step.item())
+            self._graph_ahead = False
+        if to_device:
+            self.dev_step.fill_(self.step_counter)
+
     def step(self, actions: torch.Tensor | None = None, reset_rows: torch.Tensor | None = None,
              noise: torch.Tensor | None = None, act_next: bool = False) -> int:
         """One synchronous step of all lanes; returns the slot index t it was recorded in.
@@ -273,8 +283,7 @@ class RolloutEngine:
             if self.policy is None:
                 raise RuntimeError("no policy and no actions given")
             if self._graph_ahead and not self._capturing:  # continue after graph replays
-                self.step_counter = int(self.dev_step.item())
-                self._graph_ahead = False
+                self.sync_step_counter()
             # f16x3 with the shared x0 slice: the policy launch also writes x0 (once, model 0's
             # rows) and its row exponents, as amx_assemble_input_rexp (one launch fewer per step)
             fuse_x0 = self.fuse_assembly and self.ens.W2 is not None and self.ens.shared_x0
@@ -507,9 +516,7 @@ class RolloutEngine:
             raise RuntimeError("run one eager rollout(T) before capturing")
         mmd = isinstance(self.cost, RBFLinearCost)
         c = self.ctx
-        if self._graph_ahead:
-            self.step_counter = int(self.dev_step.item())
-        self.dev_step.fill_(self.step_counter)  # the counter the next eager step would use
+        self.sync_step_counter(to_device=True)  # the counter the next eager step would use
         graphs = [torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()]
         side = torch.cuda.Stream(c.device)
         side.wait_stream(torch.cuda.current_stream(c.device))
@@ -600,9 +607,7 @@ class RolloutEngine:
         if not fused:
             raise RuntimeError("graph_rollout_overlapped needs the fused step + table reset")
         c = self.ctx
-        if self._graph_ahead:
-            self.step_counter = int(self.dev_step.item())
-        self.dev_step.fill_(self.step_counter)
+        self.sync_step_counter(to_device=True)
         graphs = [torch.cuda.CUDAGraph() for _ in range(3)]
         side = torch.cuda.Stream(c.device)
         side.wait_stream(torch.cuda.current_stream(c.device))

@@ -17,7 +17,7 @@ whether j is needed), dropped as soon as that bound reaches q, and the result is
 trajectories 1..n_i of the sequential reference, n_i = min{n : sum_{j <= n} len_j >= q}
 ('trajectories' mode: the first q).  How many run at once is set by an estimate of the
 lengths still to come (the horizon R: the reference's worst case; or, speculatively, the
-mean length of the trajectories ended so far), see _collect.  With rng='reference' every
+mean length of the trajectories ended so far), see _Admission.  With rng='reference' every
 trajectory's reset time and noise come from the reference's own seeds (the PCG64 reset draw
 per trajectory; the MT19937 policy noise from per-lane generators in the HIP library's host
 code, amx_mt_policy_noise, uploaded per chunk), so the output equals the reference's paths up
@@ -92,20 +92,6 @@ class _Store:
         self.n += m
         return base
 
-    def append(self, eng: RolloutEngine, K: int, idx: torch.Tensor) -> int:
-        m = idx.numel()
-        if self.n + m > self.cap:
-            self._alloc(max(2 * self.cap, self.n + m))
-        L = eng.B
-        s = slice(self.n, self.n + m)
-        torch.index_select(eng.obs[:K].reshape(K * L, self.S), 0, idx, out=self.obs[s])
-        torch.index_select(eng.next_obs[:K].reshape(K * L, self.S), 0, idx, out=self.nxt[s])
-        torch.index_select(eng.acts[:K].reshape(K * L, self.A), 0, idx, out=self.act[s])
-        torch.index_select(eng.means[:K].reshape(K * L, self.A), 0, idx, out=self.mean[s])
-        base = self.n
-        self.n += m
-        return base
-
 
 class _FreeLanes:
     """The idle lanes.  Member-blocked engines (RolloutEngine.member_blocks = Bq: lane b runs
@@ -129,6 +115,135 @@ class _FreeLanes:
 
     def put(self, lane: int) -> None:
         self.lists[lane // self.Bq if self.Bq else 0].append(lane)
+
+
+class _Admission:
+    """Which trajectory runs on which lane: the host-side state of one sample_points call (plain
+    Python: no torch, no engine, no device).
+
+    A worker's trajectories are admitted in seed order j.  Trajectory j is needed iff the exact
+    lengths of 1..j-1 sum to less than the quota q; the lengths reached so far give a lower bound
+    LB_j of that sum, so j is admitted only while LB_j < q and an in-flight trajectory whose
+    LB_j >= q is provably not needed and is dropped (its lane freed).  Among admissible
+    trajectories the concurrency is capped by an estimate: sum over the admitted of (final length,
+    or max(length so far, L^)) < q, with L^ = the horizon R (speculate=False: the reference's
+    worst case, never wasted work) or the mean length of the trajectories ended so far
+    (speculate=True: short trajectories admit more at once; any surplus trajectory completes or is
+    dropped and never enters the result).  Each trajectory is exact-seeded, so its transitions do
+    not depend on when or on which lane it ran: the result is trajectories 1..n_i of every worker,
+    n_i = min{n : sum_{j <= n} len_j >= q}, for any admission order and any lag between a chunk's
+    launch and its advance()."""
+
+    def __init__(self, W: int, quota: int, mode: str, base_seed: int, R: int, speculate: bool, L: int, M: int,
+                 Bq: int):
+        self.W, self.quota, self.mode, self.base_seed, self.R, self.speculate = W, quota, mode, base_seed, R, speculate
+        self.adm: list[list[_Traj]] = [[] for _ in range(W)]   # admitted trajectories, in j order
+        self.next_j = [1] * W
+        self.done_w = [False] * W
+        self.lane_tr: list[_Traj | None] = [None] * L
+        self.free = _FreeLanes(L, M, Bq)
+        self.ended_sum, self.ended_n = 0, 0
+
+    def _drop(self, tr: _Traj) -> None:
+        if tr.lane >= 0:
+            self.lane_tr[tr.lane] = None
+            self.free.put(tr.lane)
+            tr.lane = -1
+
+    def admit(self) -> list[_Traj]:
+        """Per worker: drop the unneeded, detect completion, admit (round-robin).  Returns the
+        newly admitted trajectories, each on its lane."""
+        W, quota, mode, adm, done_w, free = self.W, self.quota, self.mode, self.adm, self.done_w, self.free
+        # speculation: 2x the worst-case concurrency until lengths are known (lanes are nearly free
+        # at these counts: the step time is latency-bound), then the mean ended length
+        lhat = (float(self.R) if not self.speculate
+                else (self.ended_sum / self.ended_n if self.ended_n >= 4 else 0.5 * self.R))
+        for w in range(W):
+            if done_w[w]:
+                continue
+            trs = adm[w]
+            if mode == "samples":
+                lb, cut = 0, len(trs)
+                for i, tr in enumerate(trs):
+                    if lb >= quota:
+                        cut = i
+                        break
+                    lb += tr.length
+                for tr in trs[cut:]:
+                    self._drop(tr)
+                del trs[cut:]
+                if trs and all(tr.ended for tr in trs) and sum(tr.length for tr in trs) >= quota:
+                    done_w[w] = True
+            elif len(trs) == quota and all(tr.ended for tr in trs):
+                done_w[w] = True
+        new = []
+        # per worker: the lower bound (lengths so far) and the estimate, summed once per chunk
+        # and extended as trajectories are admitted (a new one adds 0 and lhat)
+        lbs, ests = [0] * W, [0.0] * W
+        if mode == "samples":
+            for w in range(W):
+                if not done_w[w]:
+                    lbs[w] = sum(tr.length for tr in adm[w])
+                    ests[w] = sum(tr.length if tr.ended else max(tr.length, lhat) for tr in adm[w])
+        progress = True
+        while free and progress:
+            progress = False
+            for w in range(W):
+                if not free or done_w[w]:
+                    continue
+                trs = adm[w]
+                ok = (lbs[w] < quota and ests[w] < quota) if mode == "samples" else len(trs) < quota
+                if ok:
+                    j = self.next_j[w]
+                    lane = free.take(j)
+                    if lane < 0:  # (member-blocked: j waits for a lane of its member's block)
+                        continue
+                    self.next_j[w] += 1
+                    tr = _Traj(w, j, 12345 + self.base_seed * w + j)
+                    tr.lane = lane
+                    self.lane_tr[tr.lane] = tr
+                    trs.append(tr)
+                    new.append(tr)
+                    ests[w] += max(0, lhat)
+                    progress = True
+        return new
+
+    def in_flight(self) -> list[tuple[int, _Traj]]:
+        """The (lane, trajectory) pairs of the active lanes, in lane order."""
+        return [(b, tr) for b, tr in enumerate(self.lane_tr) if tr is not None]
+
+    def live(self, launched: list[tuple[int, _Traj]]) -> list[tuple[int, _Traj]]:
+        """Of the pairs a chunk was launched with, those whose trajectory is still running on its
+        lane (not ended in an earlier chunk, not dropped): the ones the chunk's steps belong to."""
+        return [(b, tr) for b, tr in launched if not tr.ended and tr.lane == b]
+
+    def advance(self, live: list[tuple[int, _Traj]], n, hit, rows) -> None:
+        """A chunk's outcome for its live() pairs: pair i ran n[i] more steps, kept at store row
+        rows[i] on, and ended iff hit[i] (its lane is freed)."""
+        for (_, tr), n_i, h, row in zip(live, n.tolist(), hit.tolist(), rows.tolist()):
+            tr.segs.append((row, n_i))
+            tr.length += n_i
+            if h:
+                tr.ended = True
+                self.ended_sum += tr.length
+                self.ended_n += 1
+                self._drop(tr)
+
+    def trajectories(self) -> list[_Traj]:
+        """The result, in (worker, j) order."""
+        return [tr for trs in self.adm for tr in trs]
+
+
+def _chunk_rows(done: np.ndarray, lanes: np.ndarray, L: int):
+    """done [K, n] (bool) of the n lanes `lanes` over a chunk's K steps of L lanes -> per lane the
+    steps it ran (through its first done step; K if none) and whether it ended, and for the
+    compacted rows (lane after lane, each in step order) every lane's first row `starts` and the
+    rows' indices step * L + lane into the flat [K * L] chunk arrays."""
+    hit = done.any(axis=0)
+    n = np.where(hit, done.argmax(axis=0) + 1, done.shape[0])
+    starts = np.cumsum(n) - n
+    step_of = np.arange(int(n.sum())) - np.repeat(starts, n)
+    return n, hit, starts, step_of * L + np.repeat(lanes, n)
 
 
 def _reset_time_max(env) -> float:
@@ -227,13 +342,11 @@ class _HostNoise:
     def __init__(self, lib, L: int, K: int, A: int):
         self.lib, self.L, self.K, self.A = lib, L, K, A
         self.states = np.zeros((L, N.AMX_MT_STATE_BYTES), np.uint8)
-        # pinned buffers: the next chunk's noise is drawn into one while another's upload and the
-        # current chunk's steps run on the GPU (the pipelined collector rotates three: chunk
+        # pinned buffers, chunk c's in bufs[c % 3]: the next chunk's noise is drawn into one while
+        # another's upload and the current chunk's steps run on the GPU (three: pipelined, chunk
         # c + 1's draw starts before chunk c - 1 has been read back)
         pin = torch.cuda.is_available()
         self.bufs = [torch.zeros(K, L, A, dtype=torch.float64, pin_memory=pin) for _ in range(3)]
-        self.cur = 0
-        self.ahead = -1  # buffer already holding the continuing lanes' next draws (draw_async)
         self._thread, self._err = None, None
 
     def seed(self, lanes: np.ndarray, seeds: np.ndarray) -> None:
@@ -253,10 +366,14 @@ class _HostNoise:
                 "amx_mt_policy_noise")
         return buf
 
-    # background draws (the pipelined collector): the next chunk's noise of the lanes in flight,
-    # drawn on a host thread (the ctypes call releases the GIL) while the main thread reads the
-    # previous chunk and admits; join() before any seed or draw touches the generator states
-    def draw_async(self, lanes: np.ndarray, which: int) -> None:
+    def draw_ahead(self, lanes: np.ndarray, which: int, background: bool) -> None:
+        """The next chunk's noise of the lanes in flight into bufs[which], while the GPU steps.
+        background (the pipelined collector): on a host thread (the ctypes call releases the GIL)
+        while the main thread reads the previous chunk and admits; join() before any seed or
+        draw touches the generator states."""
+        if not background:
+            self.draw(lanes, self.bufs[which])
+            return
         self.join()
         self._err = None
 
@@ -267,10 +384,9 @@ class _HostNoise:
                 self._err = e
         self._thread = threading.Thread(target=run, daemon=True)
         self._thread.start()
-        self.ahead = which
 
     def join(self) -> None:
-        th = getattr(self, "_thread", None)
+        th = self._thread
         if th is not None:
             th.join()
             self._thread = None
@@ -289,9 +405,7 @@ class _ChunkGraph:
         # a reference cycle that only the garbage collector frees)
         self.eng, self.K = weakref.proxy(eng), K
         self.g = torch.cuda.CUDAGraph()
-        if eng._graph_ahead:
-            eng.step_counter = int(eng.dev_step.item())
-        eng.dev_step.fill_(eng.step_counter)
+        eng.sync_step_counter(to_device=True)
         side = torch.cuda.Stream(c.device)
         side.wait_stream(torch.cuda.current_stream(c.device))
         t0 = eng.t
@@ -403,8 +517,7 @@ def _chunk_graph(eng: RolloutEngine, K: int, noise_dev, eval_mode: bool) -> _Chu
         g = cache[key] = _ChunkGraph(eng, K, noise_dev)
     else:
         eng.begin_rollout()
-        if eng._graph_ahead:
-            eng.step_counter = int(eng.dev_step.item())
+        eng.sync_step_counter()
     return g
 
 
@@ -417,177 +530,10 @@ def _noise_buffer(eng: RolloutEngine, K: int, L: int, A: int) -> torch.Tensor:
     return buf
 
 
-def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, rng: str, eval_mode: bool,
-             time_max: float, speculate: bool = True, graph: bool = True):
-    """Run the W workers' trajectory sequences on the engine's lanes (see the module notes).
-
-    Admission: a worker's trajectories are admitted in seed order j.  Trajectory j is needed iff
-    the exact lengths of 1..j-1 sum to less than the quota q; the lengths reached so far give a
-    lower bound LB_j of that sum, so j is admitted only while LB_j < q and an in-flight
-    trajectory whose LB_j >= q is provably not needed and is dropped (its lane freed).  Among
-    admissible trajectories the concurrency is capped by an estimate: sum over the admitted of
-    (final length, or max(length so far, L^)) < q, with L^ = the horizon R (speculate=False: the
-    reference's worst case, never wasted work) or the mean length of the trajectories ended so far
-    (speculate=True: short trajectories admit more at once; any surplus trajectory completes or is
-    dropped and never enters the result).  Each trajectory is exact-seeded, so its transitions do
-    not depend on when or on which lane it ran: the result is trajectories 1..n_i of every worker,
-    n_i = min{n : sum_{j <= n} len_j >= q}, for any admission order."""
-    c = eng.ctx
-    L, S, A, K, dev = eng.B, c.S, c.A, eng.K, c.device
-    R = eng.term.horizon
-    motion = eng.motion
-    adm: list[list[_Traj]] = [[] for _ in range(W)]   # admitted trajectories, in j order
-    next_j = [1] * W
-    done_w = [False] * W
-    lane_tr: list[_Traj | None] = [None] * L
-    free = _FreeLanes(L, c.M, eng.member_blocks)
-    store = _Store(dev, S, A, W * (quota + R) if mode == "samples" else W * quota * 64)
-    eng.eval_mode = eval_mode
-    ref_noise = rng == "reference" and not eval_mode
-    hn = _HostNoise(c.lib, L, K, A) if ref_noise else None
-    noise_dev = _noise_buffer(eng, K, L, A) if ref_noise else None
-    pin = torch.cuda.is_available()
-    # per-chunk reset inputs: staged in pinned memory, uploaded without a host wait
-    mask_h = torch.zeros(L, dtype=torch.uint8, pin_memory=pin)
-    counts_h = torch.zeros(L, dtype=torch.int32, pin_memory=pin)
-    rows_h = torch.zeros(L, dtype=torch.float64 if motion is not None else torch.int32, pin_memory=pin)
-    mask_dev = torch.empty(L, dtype=torch.uint8, device=dev)
-    counts_dev = torch.empty(L, dtype=torch.int32, device=dev)
-    rows_dev = torch.empty(L, dtype=rows_h.dtype, device=dev)
-    mask_np, counts_np, rows_np = mask_h.numpy(), counts_h.numpy(), rows_h.numpy()
-    pre_drawn = False
-    ended_sum, ended_n = 0, 0
-    chunk_graph = None
-    chunks, budget = 0, 4 * (W * quota + W) * (R + K) // K + 64
-
-    def drop(tr: _Traj) -> None:
-        if tr.lane >= 0:
-            lane_tr[tr.lane] = None
-            free.put(tr.lane)
-            tr.lane = -1
-
-    while True:
-        # ---- per worker: drop the unneeded, detect completion, admit (round-robin) ----
-        # speculation: 2x the worst-case concurrency until lengths are known (lanes are nearly free
-        # at these counts: the step time is latency-bound), then the mean ended length
-        lhat = float(R) if not speculate else (ended_sum / ended_n if ended_n >= 4 else 0.5 * R)
-        for w in range(W):
-            if done_w[w]:
-                continue
-            trs = adm[w]
-            if mode == "samples":
-                lb, cut = 0, len(trs)
-                for i, tr in enumerate(trs):
-                    if lb >= quota:
-                        cut = i
-                        break
-                    lb += tr.length
-                for tr in trs[cut:]:
-                    drop(tr)
-                del trs[cut:]
-                if trs and all(tr.ended for tr in trs) and sum(tr.length for tr in trs) >= quota:
-                    done_w[w] = True
-            elif len(trs) == quota and all(tr.ended for tr in trs):
-                done_w[w] = True
-        new = []
-        # per worker: the lower bound (lengths so far) and the estimate, summed once per chunk
-        # and extended as trajectories are admitted (a new one adds 0 and lhat)
-        lbs, ests = [0] * W, [0.0] * W
-        if mode == "samples":
-            for w in range(W):
-                if not done_w[w]:
-                    lbs[w] = sum(tr.length for tr in adm[w])
-                    ests[w] = sum(tr.length if tr.ended else max(tr.length, lhat) for tr in adm[w])
-        progress = True
-        while free and progress:
-            progress = False
-            for w in range(W):
-                if not free or done_w[w]:
-                    continue
-                trs = adm[w]
-                ok = (lbs[w] < quota and ests[w] < quota) if mode == "samples" else len(trs) < quota
-                if ok:
-                    j = next_j[w]
-                    lane = free.take(j)
-                    if lane < 0:  # (member-blocked: j waits for a lane of its member's block)
-                        continue
-                    next_j[w] += 1
-                    tr = _Traj(w, j, 12345 + base_seed * w + j)
-                    tr.lane = lane
-                    lane_tr[tr.lane] = tr
-                    trs.append(tr)
-                    new.append(tr)
-                    ests[w] += max(0, lhat)
-                    progress = True
-        active = np.array([b for b in range(L) if lane_tr[b] is not None], np.int64)
-        if active.size == 0:
-            break
-        chunks += 1
-        if chunks > budget:
-            raise RuntimeError("sample_points: step budget exhausted (trajectories longer than the horizon?)")
-        # ---- resets: the new trajectories (reset counter j-1 -> member j mod M) and the idle lanes ----
-        eng.begin_rollout()
-        mask_np.fill(1)
-        mask_np[active] = 0
-        counts_np.fill(0)
-        new_lanes = np.array([tr.lane for tr in new], np.int64)
-        for tr in new:
-            mask_np[tr.lane] = 1
-            counts_np[tr.lane] = tr.j - 1
-            if rng == "reference":
-                t = _gym_np_random(tr.seed).uniform(low=0, high=time_max)  # seed_env + reset (sim_env.py:132,276)
-                rows_np[tr.lane] = t if motion is not None else int(np.floor(t))
-        mask_dev.copy_(mask_h, non_blocking=True)
-        counts_dev.copy_(counts_h, non_blocking=True)
-        # reset lanes restart their counter at j - 1 (idle lanes at 0); the reset kernel adds one
-        torch.where(mask_dev.bool(), counts_dev, eng.reset_count, out=eng.reset_count)
-        if rng == "reference":
-            rows_dev.copy_(rows_h, non_blocking=True)
-        eng.reset_lanes(mask_dev, rows_dev if rng == "reference" else None)
-        # ---- K synchronous steps ----
-        if hn is not None:
-            if new:
-                hn.seed(new_lanes, np.array([tr.seed for tr in new]))  # np.random.seed (sampler.py:39)
-            buf = hn.bufs[hn.cur]
-            hn.draw(new_lanes if pre_drawn else active, buf)  # (the continuing lanes' noise is drawn)
-            noise_dev.copy_(buf, non_blocking=True)
-        # (the first chunk of a new shape allocates the workspaces: captured from the second on)
-        if graph and chunk_graph is None and (chunks >= 2 or "_chunk_graphs" in eng.__dict__):
-            chunk_graph = _chunk_graph(eng, K, noise_dev, eval_mode)
-        if chunk_graph is not None:
-            chunk_graph.replay()
-        else:
-            for k in range(K):
-                eng.step(noise=None if noise_dev is None else noise_dev[k])
-        if hn is not None:  # the next chunk's noise of the lanes in flight, while the GPU steps
-            hn.cur ^= 1
-            hn.draw(active, hn.bufs[hn.cur])
-            pre_drawn = True
-        done = eng.done[:K].cpu().numpy().astype(bool)  # [K, L]: the chunk's one host sync
-        # ---- compact the in-flight lanes' transitions into the store (vectorised) ----
-        d = done[:, active]
-        hit = d.any(axis=0)
-        n = np.where(hit, d.argmax(axis=0) + 1, K)
-        tot = int(n.sum())
-        starts = np.cumsum(n) - n
-        step_of = np.arange(tot) - np.repeat(starts, n)
-        flat = step_of * L + np.repeat(active, n)
-        base = store.append(eng, K, torch.from_numpy(flat).to(dev))
-        for i, b in enumerate(active.tolist()):
-            tr = lane_tr[b]
-            tr.segs.append((base + int(starts[i]), int(n[i])))
-            tr.length += int(n[i])
-            if hit[i]:
-                tr.ended = True
-                ended_sum += tr.length
-                ended_n += 1
-                drop(tr)
-    # ---- reorder into path order on the device, one copy to the host ----
-    trajs = [tr for w in range(W) for tr in adm[w]]
-    if not trajs:
-        return [], 0
-    return _build_paths(trajs, store, eng, dev)
-
+def _chunk_arrays(eng: RolloutEngine, K: int):
+    """The engine's records (obs, next_obs, acts, means) of a chunk's K steps as flat [K * L] rows."""
+    m = K * eng.B
+    return tuple(x[:K].reshape(m, x.shape[-1]) for x in (eng.obs, eng.next_obs, eng.acts, eng.means))
 
 
 class _ChunkRing:
@@ -596,198 +542,144 @@ class _ChunkRing:
     done flags are read; chunk i's rows are compacted from its slot one iteration later."""
 
     def __init__(self, eng: RolloutEngine, K: int):
-        c = eng.ctx
-        m = K * eng.B
-        z = lambda w, dt: torch.empty(m, w, dtype=dt, device=c.device)
-        self.slots = [(z(c.S, torch.float64), z(c.S, torch.float64), z(c.A, torch.float64), z(c.A, torch.float32))
-                      for _ in range(2)]
-        self.K, self.m = K, m
+        self.slots = [tuple(torch.empty_like(x) for x in _chunk_arrays(eng, K)) for _ in range(2)]
+        self.K = K
 
     def snapshot(self, eng: RolloutEngine, si: int) -> None:
-        K, m = self.K, self.m
-        for dst, src in zip(self.slots[si], (eng.obs, eng.next_obs, eng.acts, eng.means)):
-            dst.copy_(src[:K].reshape(m, dst.shape[1]))
+        for dst, src in zip(self.slots[si], _chunk_arrays(eng, self.K)):
+            dst.copy_(src)
 
 
-def _collect_pipelined(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, rng: str,
-                       eval_mode: bool, time_max: float, speculate: bool = True, graph: bool = True):
-    """_collect with the host one chunk behind the GPU: chunk i is queued (resets, noise, the
-    captured steps, a raw copy of its transitions and an async copy of its done flags) before
-    chunk i-1's done flags are read and its trajectories advanced.  Admission therefore sees
-    the results through chunk i-2: a lane whose trajectory ended in chunk i-1 runs chunk i
-    idle (its steps are never attributed: each chunk keeps the lane -> trajectory map it was
-    launched with) and is re-admitted one chunk later.  Trajectories are exact-seeded, so the
-    result is _collect's (the same trajectories 1..n_i per worker, the same transitions)."""
+class _Stage:
+    """One set of pinned host staging for a chunk: its reset inputs and, with read_back (the
+    pipelined collector), its done flags, the event of their copy and its compaction indices."""
+
+    def __init__(self, L: int, K: int, rows_dtype, dev, read_back: bool):
+        pin = torch.cuda.is_available()
+        self.mask = torch.zeros(L, dtype=torch.uint8, pin_memory=pin)
+        self.counts = torch.zeros(L, dtype=torch.int32, pin_memory=pin)
+        self.rows = torch.zeros(L, dtype=rows_dtype, pin_memory=pin)
+        if read_back:
+            self.done = torch.zeros(K, L, dtype=torch.uint8, pin_memory=pin)
+            self.event = torch.cuda.Event() if pin else None
+            self.flat = torch.zeros(K * L, dtype=torch.int64, pin_memory=pin)
+            self.flat_dev = torch.empty(K * L, dtype=torch.int64, device=dev)
+
+
+def _reset_lanes(eng: RolloutEngine, st: _Stage, devs, active: np.ndarray, new: list, rng: str,
+                 time_max: float) -> None:
+    """A chunk's resets: the new trajectories' lanes (reset counter j - 1 -> member j mod M; with
+    rng='reference' at the reset time drawn from the trajectory's seed) and the idle lanes, staged
+    in `st` and uploaded into devs = (mask, counts, rows) without a host wait."""
+    mask_dev, counts_dev, rows_dev = devs
+    mask_np, counts_np, rows_np = st.mask.numpy(), st.counts.numpy(), st.rows.numpy()
+    eng.begin_rollout()
+    mask_np.fill(1)
+    mask_np[active] = 0
+    counts_np.fill(0)
+    for tr in new:
+        mask_np[tr.lane] = 1
+        counts_np[tr.lane] = tr.j - 1
+        if rng == "reference":
+            t = _gym_np_random(tr.seed).uniform(low=0, high=time_max)  # seed_env + reset (sim_env.py:132,276)
+            rows_np[tr.lane] = t if eng.motion is not None else int(np.floor(t))
+    mask_dev.copy_(st.mask, non_blocking=True)
+    counts_dev.copy_(st.counts, non_blocking=True)
+    # reset lanes restart their counter at j - 1 (idle lanes at 0); the reset kernel adds one
+    torch.where(mask_dev.bool(), counts_dev, eng.reset_count, out=eng.reset_count)
+    if rng == "reference":
+        rows_dev.copy_(st.rows, non_blocking=True)
+    eng.reset_lanes(mask_dev, rows_dev if rng == "reference" else None)
+
+
+def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, rng: str, eval_mode: bool,
+             time_max: float, speculate: bool = True, graph: bool = True, pipeline: bool = True):
+    """Run the W workers' trajectory sequences on the engine's lanes (see the module notes and
+    _Admission): admit, launch a chunk (resets, noise, the K steps), read a chunk back (its done
+    flags; its in-flight rows compacted into the store; its trajectories advanced).
+
+    pipeline=False reads chunk i back before chunk i + 1 is queued: one blocking read of the done
+    flags per chunk, the rows compacted straight from the engine's buffers.  pipeline=True keeps
+    the host one chunk behind the GPU: chunk i is queued (with a raw copy of its transitions and an
+    async copy of its done flags) before chunk i-1 is read back.  Admission then sees the results
+    through chunk i-2: a lane whose trajectory ended in chunk i-1 runs chunk i idle (its steps are
+    never attributed: each chunk keeps the lane -> trajectory pairs it was launched with) and is
+    re-admitted one chunk later.  Trajectories are exact-seeded, so both give the same
+    trajectories 1..n_i per worker with the same transitions."""
     c = eng.ctx
     L, S, A, K, dev = eng.B, c.S, c.A, eng.K, c.device
     R = eng.term.horizon
-    motion = eng.motion
-    adm: list[list[_Traj]] = [[] for _ in range(W)]
-    next_j = [1] * W
-    done_w = [False] * W
-    lane_tr: list[_Traj | None] = [None] * L
-    free = _FreeLanes(L, c.M, eng.member_blocks)
+    adm = _Admission(W, quota, mode, base_seed, R, speculate, L, c.M, eng.member_blocks)
     store = _Store(dev, S, A, W * (quota + R) if mode == "samples" else W * quota * 64)
-    ring = _ChunkRing(eng, K)
+    ring = _ChunkRing(eng, K) if pipeline else None
     eng.eval_mode = eval_mode
     ref_noise = rng == "reference" and not eval_mode
     hn = _HostNoise(c.lib, L, K, A) if ref_noise else None
     noise_dev = _noise_buffer(eng, K, L, A) if ref_noise else None
-    pin = torch.cuda.is_available()
-    # two sets of pinned staging: set i % 2 is rewritten only after chunk i - 2 has completed
-    stage = []
-    for _ in range(2):
-        mh = torch.zeros(L, dtype=torch.uint8, pin_memory=pin)
-        ch = torch.zeros(L, dtype=torch.int32, pin_memory=pin)
-        rh = torch.zeros(L, dtype=torch.float64 if motion is not None else torch.int32, pin_memory=pin)
-        dh = torch.zeros(K, L, dtype=torch.uint8, pin_memory=pin)
-        fh = torch.zeros(K * L, dtype=torch.int64, pin_memory=pin)  # compaction indices (async upload)
-        stage.append((mh, ch, rh, dh, torch.cuda.Event() if pin else None, fh,
-                      torch.empty(K * L, dtype=torch.int64, device=dev)))
-    mask_dev = torch.empty(L, dtype=torch.uint8, device=dev)
-    counts_dev = torch.empty(L, dtype=torch.int32, device=dev)
-    rows_dev = torch.empty(L, dtype=stage[0][2].dtype, device=dev)
-    ended_sum, ended_n = 0, 0
+    # pinned staging; pipelined two sets: set i % 2 is rewritten only after chunk i - 2 has completed
+    rows_dtype = torch.float64 if eng.motion is not None else torch.int32
+    stage = [_Stage(L, K, rows_dtype, dev, pipeline) for _ in range(2 if pipeline else 1)]
+    reset_devs = (torch.empty(L, dtype=torch.uint8, device=dev), torch.empty(L, dtype=torch.int32, device=dev),
+                  torch.empty(L, dtype=rows_dtype, device=dev))
+    pre_drawn = False  # the lanes of the previous chunk already hold their next K draws
     chunk_graph = None
     chunks, budget = 0, 4 * (W * quota + W) * (R + K) // K + 64
-    pending = None  # (set index, [(lane, trajectory)]) of the queued, unread chunk
+    pending = None  # pipelined: (stage set, [(lane, trajectory)], lanes) of the queued, unread chunk
 
-    def drop(tr: _Traj) -> None:
-        if tr.lane >= 0:
-            lane_tr[tr.lane] = None
-            free.put(tr.lane)
-            tr.lane = -1
-
-    def process(p) -> None:
-        nonlocal ended_sum, ended_n
-        si, launched = p
-        ev = stage[si][4]
-        if ev is not None:
-            ev.synchronize()
-        # lanes whose trajectory is still running on them (not ended earlier, not dropped)
-        live = [(b, tr) for b, tr in launched if not tr.ended and tr.lane == b]
+    def read_back(si: int, launched, lanes: np.ndarray) -> None:
+        st = stage[si]
+        if not pipeline:
+            done = eng.done[:K].cpu().numpy()  # [K, L]: the chunk's one host sync
+        else:
+            if st.event is not None:
+                st.event.synchronize()
+            done = st.done.numpy()
+        live = adm.live(launched)
         if not live:
             return
-        lanes = np.array([b for b, _ in live], np.int64)
-        d = stage[si][3].numpy().astype(bool)[:, lanes]  # [K, n live]
-        hit = d.any(axis=0)
-        n = np.where(hit, d.argmax(axis=0) + 1, K)
-        starts = np.cumsum(n) - n
-        step_of = np.arange(int(n.sum())) - np.repeat(starts, n)
-        flat = step_of * L + np.repeat(lanes, n)
-        # pinned + non_blocking: a pageable upload would wait for the chunk queued behind this one
-        fh, fd = stage[si][5], stage[si][6]
-        fh.numpy()[:flat.size] = flat
-        fd[:flat.size].copy_(fh[:flat.size], non_blocking=True)
-        base = store.append_from(ring.slots[si], fd[:flat.size])
-        for i, (b, tr) in enumerate(live):
-            tr.segs.append((base + int(starts[i]), int(n[i])))
-            tr.length += int(n[i])
-            if hit[i]:
-                tr.ended = True
-                ended_sum += tr.length
-                ended_n += 1
-                drop(tr)
+        if len(live) < len(launched):
+            lanes = np.array([b for b, _ in live], np.int64)
+        n, hit, starts, flat = _chunk_rows(done.astype(bool)[:, lanes], lanes, L)
+        # ---- compact the live lanes' transitions into the store ----
+        if not pipeline:
+            base = store.append_from(_chunk_arrays(eng, K), torch.from_numpy(flat).to(dev))
+        else:
+            # pinned + non_blocking: a pageable upload would wait for the chunk queued behind this one
+            st.flat.numpy()[:flat.size] = flat
+            idx = st.flat_dev[:flat.size]
+            idx.copy_(st.flat[:flat.size], non_blocking=True)
+            base = store.append_from(ring.slots[si], idx)
+        adm.advance(live, n, hit, base + starts)
 
     while True:
-        lhat = float(R) if not speculate else (ended_sum / ended_n if ended_n >= 4 else 0.5 * R)
-        for w in range(W):
-            if done_w[w]:
-                continue
-            trs = adm[w]
-            if mode == "samples":
-                lb, cut = 0, len(trs)
-                for i, tr in enumerate(trs):
-                    if lb >= quota:
-                        cut = i
-                        break
-                    lb += tr.length
-                for tr in trs[cut:]:
-                    drop(tr)
-                del trs[cut:]
-                if trs and all(tr.ended for tr in trs) and sum(tr.length for tr in trs) >= quota:
-                    done_w[w] = True
-            elif len(trs) == quota and all(tr.ended for tr in trs):
-                done_w[w] = True
-        new = []
-        # per worker: the lower bound (lengths so far) and the estimate, summed once per chunk
-        # and extended as trajectories are admitted (a new one adds 0 and lhat)
-        lbs, ests = [0] * W, [0.0] * W
-        if mode == "samples":
-            for w in range(W):
-                if not done_w[w]:
-                    lbs[w] = sum(tr.length for tr in adm[w])
-                    ests[w] = sum(tr.length if tr.ended else max(tr.length, lhat) for tr in adm[w])
-        progress = True
-        while free and progress:
-            progress = False
-            for w in range(W):
-                if not free or done_w[w]:
-                    continue
-                trs = adm[w]
-                ok = (lbs[w] < quota and ests[w] < quota) if mode == "samples" else len(trs) < quota
-                if ok:
-                    j = next_j[w]
-                    lane = free.take(j)
-                    if lane < 0:  # (member-blocked: j waits for a lane of its member's block)
-                        continue
-                    next_j[w] += 1
-                    tr = _Traj(w, j, 12345 + base_seed * w + j)
-                    tr.lane = lane
-                    lane_tr[tr.lane] = tr
-                    trs.append(tr)
-                    new.append(tr)
-                    ests[w] += max(0, lhat)
-                    progress = True
-        active = np.array([b for b in range(L) if lane_tr[b] is not None], np.int64)
+        new = adm.admit()
+        launched = adm.in_flight()
         # nothing to admit and every trajectory in flight reaches the horizon inside the queued
         # chunk (its length through the chunks read back + K >= R): another chunk would only step
         # idle lanes -- read the queued one back first
-        tail = (pending is not None and not new
-                and all(lane_tr[b].length + K >= R for b in active.tolist()))
-        if active.size == 0 or tail:
+        tail = pending is not None and not new and all(tr.length + K >= R for _, tr in launched)
+        if not launched or tail:
             if pending is None:
                 break
-            process(pending)  # the last queued chunk may end trajectories or free admissions
+            read_back(*pending)  # the last queued chunk may end trajectories or free admissions
             pending = None
             continue
         chunks += 1
         if chunks > budget:
             raise RuntimeError("sample_points: step budget exhausted (trajectories longer than the horizon?)")
-        si = chunks & 1
-        mask_h, counts_h, rows_h, done_h, ev = stage[si][:5]
-        mask_np, counts_np, rows_np = mask_h.numpy(), counts_h.numpy(), rows_h.numpy()
-        eng.begin_rollout()
-        mask_np.fill(1)
-        mask_np[active] = 0
-        counts_np.fill(0)
+        si = chunks % len(stage)
+        st = stage[si]
+        active = np.array([b for b, _ in launched], np.int64)
         new_lanes = np.array([tr.lane for tr in new], np.int64)
-        for tr in new:
-            mask_np[tr.lane] = 1
-            counts_np[tr.lane] = tr.j - 1
-            if rng == "reference":
-                t = _gym_np_random(tr.seed).uniform(low=0, high=time_max)  # seed_env + reset (sim_env.py:132,276)
-                rows_np[tr.lane] = t if motion is not None else int(np.floor(t))
-        mask_dev.copy_(mask_h, non_blocking=True)
-        counts_dev.copy_(counts_h, non_blocking=True)
-        torch.where(mask_dev.bool(), counts_dev, eng.reset_count, out=eng.reset_count)
-        if rng == "reference":
-            rows_dev.copy_(rows_h, non_blocking=True)
-        eng.reset_lanes(mask_dev, rows_dev if rng == "reference" else None)
+        _reset_lanes(eng, st, reset_devs, active, new, rng, time_max)
+        # ---- K synchronous steps ----
         if hn is not None:
-            nb = chunks % 3
-            buf = hn.bufs[nb]
-            if hn.ahead == nb:  # the lanes of the previous chunk were drawn in the background
-                hn.join()
-                hn.ahead = -1
-                if new:
-                    hn.seed(new_lanes, np.array([tr.seed for tr in new]))  # np.random.seed (sampler.py:39)
-                    hn.draw(new_lanes, buf)
-            else:
-                hn.join()
-                if new:
-                    hn.seed(new_lanes, np.array([tr.seed for tr in new]))
-                hn.draw(active, buf)  # the next K draws of every lane in flight (finished ones idle)
+            hn.join()
+            if new:
+                hn.seed(new_lanes, np.array([tr.seed for tr in new]))  # np.random.seed (sampler.py:39)
+            # the next K draws of every lane in flight (finished ones idle), the continuing lanes'
+            # drawn ahead during the previous chunk
+            buf = hn.draw(new_lanes if pre_drawn else active, hn.bufs[chunks % 3])
             noise_dev.copy_(buf, non_blocking=True)
         # (the first chunk of a new shape allocates the workspaces: captured from the second on)
         if graph and chunk_graph is None and (chunks >= 2 or "_chunk_graphs" in eng.__dict__):
@@ -797,26 +689,32 @@ def _collect_pipelined(eng: RolloutEngine, W: int, quota: int, mode: str, base_s
         else:
             for k in range(K):
                 eng.step(noise=None if noise_dev is None else noise_dev[k])
-        ring.snapshot(eng, si)
-        done_h.copy_(eng.done[:K], non_blocking=True)
-        if ev is not None:
-            ev.record()
+        if pipeline:
+            ring.snapshot(eng, si)
+            st.done.copy_(eng.done[:K], non_blocking=True)
+            if st.event is not None:
+                st.event.record()
         if hn is not None:
-            # the next chunk's draws of this chunk's lanes, on a host thread while chunk c - 1 is
-            # read back (buffer (c + 1) % 3 last served chunk c - 2, whose upload completed before
-            # process() returned for it); a lane that ends or is dropped is re-seeded and re-drawn
-            # if admitted again, so its surplus draws are never used
-            hn.draw_async(active, (chunks + 1) % 3)
-        launched = [(int(b), lane_tr[b]) for b in active.tolist()]
+            # the next chunk's draws of this chunk's lanes while the GPU steps (pipelined: on a host
+            # thread while chunk c - 1 is read back; buffer (c + 1) % 3 last served chunk c - 2,
+            # whose upload completed before it was read back); a lane that ends or is dropped is
+            # re-seeded and re-drawn if admitted again, so its surplus draws are never used
+            hn.draw_ahead(active, (chunks + 1) % 3, background=pipeline)
+            pre_drawn = True
+        if not pipeline:
+            read_back(si, launched, active)
+            continue
         if pending is not None:
-            process(pending)
-        pending = (si, launched)
+            read_back(*pending)
+        pending = (si, launched, active)
     if hn is not None:
         hn.join()
-    trajs = [tr for w in range(W) for tr in adm[w]]
+    # ---- reorder into path order on the device, one copy to the host ----
+    trajs = adm.trajectories()
     if not trajs:
         return [], 0
     return _build_paths(trajs, store, eng, dev)
+
 
 def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_workers: int = 4, mode: str = "samples",
                   eval_mode: bool = False, verbose: bool = False, deepmimic: bool = False, rng: str = "reference",
@@ -830,9 +728,9 @@ def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_work
     log_std, evaluation}, env_infos, terminated).  A missing info['valid'] counts as valid
     (SimEnv returns {}; the reference's deepmimic=True branch, sampler.py:61, would raise).
     `speculate`: admit beyond the worst-case reservation from the observed trajectory lengths
-    (same result, see _collect); `graph`: replay each chunk's steps as a captured HIP graph;
-    `pipeline`: queue chunk i before reading chunk i-1's done flags (same result,
-    _collect_pipelined); `member_blocked` (f16x3 ensembles with M >= 2): every lane steps through
+    (same result, see _Admission); `graph`: replay each chunk's steps as a captured HIP graph;
+    `pipeline`: queue chunk i before reading chunk i-1's done flags (same result, see
+    _collect); `member_blocked` (f16x3 ensembles with M >= 2): every lane steps through
     its trajectory's member only, as SimEnv.step does (the engine's lanes in M blocks of a
     multiple of 128; a quarter of the ensemble rows per step at M = 4), instead of all M members
     on every lane (same paths up to the GEMM's fp32 rounding)."""
@@ -864,9 +762,8 @@ def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_work
     if rng == "device":
         policy.seed = (12345 + int(base_seed)) & 0xFFFFFFFFFFFFFFFF
     t0 = time.time()
-    collect = _collect_pipelined if pipeline else _collect
-    paths, n = (collect(eng, W, quota, mode, int(base_seed), rng, eval_mode, time_max, speculate=speculate,
-                        graph=graph)
+    paths, n = (_collect(eng, W, quota, mode, int(base_seed), rng, eval_mode, time_max, speculate=speculate,
+                         graph=graph, pipeline=pipeline)
                 if quota > 0 else ([], 0))
     if verbose:
         print(f"Collected {n} and {len(paths)} trajectories in {time.time() - t0} seconds")
