@@ -54,6 +54,8 @@ SIGNATURES = {
     "amx_assemble_input_rexp": (c_int, [vp, vp, vp, c_int, vp, c_ll, c_int, c_int, vp, c_ll, c_ll, c_int, vp]),
     "amx_gemm_bias_act": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll,
                                   vp, c_ll, vp, c_int, c_ll, c_int, c_int, vp]),
+    "amx_gemm_bias_act_t64": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll,
+                                      vp, c_ll, vp, c_int, c_ll, c_int, c_int, vp]),
     "amx_gemm_out_unnorm": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll,
                                     vp, c_ll, vp, c_int, c_ll, vp]),
     "amx_split_bf16x3": (c_int, [vp, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_ll, vp]),
@@ -140,6 +142,10 @@ SIGNATURES = {
     "amx_vfit_param_count": (c_ll, [c_int, c_int, c_int]),
     "amx_vfit_epoch": (c_int, [vp, c_int, vp, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, vp, vp, vp]),
+    "amx_efit_param_count": (c_ll, [vp]),
+    "amx_efit_work_floats": (c_ll, [vp, c_int]),
+    "amx_efit_step": (c_int, [vp, c_int, c_int, c_int, vp, c_ll, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int,
+                              c_dbl, c_dbl, c_dbl, vp, c_ll, vp, vp]),
     "amx_philox":(c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
     "amx_mt_seed": (c_int, [vp, c_int, vp, vp, c_int]),
     "amx_mt_policy_noise": (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_ll, c_ll]),
@@ -152,6 +158,7 @@ AMX_SHAPE_SPHERE, AMX_SHAPE_CAPSULE, AMX_SHAPE_BOX = 0, 1, 2
 AMX_ACT_NONE, AMX_ACT_RELU = 0, 1
 AMX_IN_F64, AMX_IN_F32 = 0, 1
 AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
+AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1
 
 
 class AmxNativeError(RuntimeError):

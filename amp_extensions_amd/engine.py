@@ -468,6 +468,162 @@ class DeviceEnsemble:
         return self.forward_preds(state, action, B)[k, :B].clone()
 
 
+    # ---- training (DynamicsModel.train_step / validate_step, dynamics.py:236-261) ------------
+    _fit = None  # training state, allocated by fit_begin
+
+    def _colmap(self) -> np.ndarray:
+        """nn.Linear input column -> padded dense-concat column."""
+        c = self.ctx
+        return np.concatenate([np.arange(c.S + c.A)] + [c.k0_pad + i * c.Hp + np.arange(self.hidden)
+                                                         for i in range(c.L)])
+
+    def _layer_dims(self, i: int):
+        """(padded rows, padded K, rows, in) of layer i."""
+        c = self.ctx
+        last = i == c.L
+        return (c.n_out_pad if last else c.Hp, c.ldk if last else c.k0_pad + i * c.Hp,
+                c.S if last else self.hidden, c.S + c.A + i * self.hidden)
+
+    def _flat_views(self, flat: torch.Tensor):
+        """[(W view [M][N_i][K_i], b view [M][N_i])] of a flat [M][param_count] training vector."""
+        out, o = [], 0
+        for i in range(self.ctx.L + 1):
+            N_, K_, _, _ = self._layer_dims(i)
+            out.append((flat[:, o:o + N_ * K_].view(-1, N_, K_), flat[:, o + N_ * K_:o + N_ * K_ + N_]))
+            o += N_ * K_ + N_
+        return out
+
+    def fit_begin(self, train_data, optim: str, lr: float, p1: float, batch_size: int, val_data=None,
+                  opt_state=None, num_models: int | None = None, hidden_sizes=None) -> None:
+        """Allocate the training state (gradients, optimizer state in the padded layout, the step
+        workspace for batches of `batch_size`, the datasets on the device) and upload `opt_state`
+        (per member {'step': int, 's1': [(W, b), ...], 's2': [...]} in nn.Linear layout, or None
+        for a fresh optimizer).  `train_data` / `val_data` = (states, actions, next_states).
+        optim 'adam' (p1 = eps) or 'sgd' (p1 = momentum, nesterov).  Everything is validated
+        before anything is allocated or launched."""
+        c = self.ctx
+        if num_models is not None and num_models != c.M:
+            raise ValueError(f"training {num_models} members on a context of {c.M}")
+        if hidden_sizes is not None and (len(set(hidden_sizes)) != 1 or len(hidden_sizes) != c.L
+                                         or hidden_sizes[0] != self.hidden):
+            raise NotImplementedError(f"the device ensemble trains equal hidden widths ({c.L} x {self.hidden}), "
+                                      f"got {list(hidden_sizes)}")
+        if optim not in ("adam", "sgd"):
+            raise NotImplementedError(f"optimizer {optim!r} (supported: 'adam', 'sgd')")
+        if not lr > 0 or (optim == "adam" and not p1 > 0) or (optim == "sgd" and not p1 >= 0):
+            raise ValueError(f"lr={lr}, {'eps' if optim == 'adam' else 'momentum'}={p1}")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size={batch_size}")
+        data = {}
+        for name, d in (("train", train_data), ("val", val_data)):
+            if d is None:
+                continue
+            s, a, s2 = [torch.as_tensor(x) for x in d]
+            n = s.shape[0]
+            if n < 1 or tuple(s.shape) != (n, c.S) or tuple(a.shape) != (n, c.A) or tuple(s2.shape) != (n, c.S):
+                raise ValueError(f"{name} data: shapes {tuple(s.shape)}, {tuple(a.shape)}, {tuple(s2.shape)} do not "
+                                 f"match S={c.S}, A={c.A}")
+            data[name] = (s, a, s2)
+        P = int(c.lib.amx_efit_param_count(c.h))
+        Bt = round_up(int(batch_size), 128)
+        floats = int(c.lib.amx_efit_work_floats(c.h, Bt))
+        if P <= 0 or floats <= 0:
+            raise N.AmxNativeError("amx_efit sizes: " + c.lib.amx_last_error().decode())
+        dev = c.device
+        f = dict(optim=optim, lr=float(lr), p1=float(p1), batch_size=int(batch_size), Bt=Bt, P=P)
+        f["data"] = {k: tuple(x.detach().to(dev, torch.float32).contiguous() for x in v) for k, v in data.items()}
+        f["grad"] = torch.zeros(c.M, P, dtype=torch.float32, device=dev)
+        f["s1"] = torch.zeros(c.M, P, dtype=torch.float32, device=dev)
+        f["s2"] = torch.zeros(c.M, P, dtype=torch.float32, device=dev) if optim == "adam" else None
+        f["step"] = torch.zeros(c.M, dtype=torch.int64, device=dev)
+        f["work"] = torch.zeros(floats, dtype=torch.float32, device=dev)
+        f["Wp"] = (N.C.c_void_p * (c.L + 1))(*[w.data_ptr() for w in self.W])
+        f["bp"] = (N.C.c_void_p * (c.L + 1))(*[b.data_ptr() for b in self.b])
+        if opt_state is not None:
+            if len(opt_state) != c.M:
+                raise ValueError(f"optimizer state of {len(opt_state)} members, expected {c.M}")
+            f["step"].copy_(torch.tensor([int(st["step"]) for st in opt_state], dtype=torch.int64))
+            cm = torch.from_numpy(self._colmap())
+            for key in ("s1", "s2"):
+                if f[key] is None:
+                    continue
+                host = torch.zeros(c.M, P, dtype=torch.float32)
+                for i, (Wv, bv) in enumerate(self._flat_views(host)):
+                    _, _, rows, n_in = self._layer_dims(i)
+                    for m, st in enumerate(opt_state):
+                        if st.get(key) is None:
+                            continue
+                        Wm, bm = st[key][i]
+                        Wv[m, :rows][:, cm[:n_in]] = torch.as_tensor(Wm).detach().float().cpu()
+                        bv[m, :rows] = torch.as_tensor(bm).detach().float().cpu()
+                f[key].copy_(host)
+        self._fit = f
+
+    def fit_epoch(self, idx, sizes, train: bool = True, grad_clip: float = 0.0, split: str = "train") -> np.ndarray:
+        """One pass of every member over its own batches, in lock step: `idx` int32
+        [M][steps][batch_size] (member g's step s takes rows idx[g, s, :sizes[s]] of the
+        `split` data), train steps or validation steps (gather, forward and loss only).
+        Returns the step losses [M][steps] (float32; one synchronisation, at the end)."""
+        f, c = self._fit, self.ctx
+        if f is None:
+            raise RuntimeError("fit_epoch before fit_begin")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        steps = len(sizes)
+        if idx.shape != (c.M, steps, f["batch_size"]) or any(not 1 <= n <= f["batch_size"] for n in sizes):
+            raise ValueError(f"idx {idx.shape} / sizes do not match [{c.M}][{steps}][{f['batch_size']}]")
+        if not grad_clip >= 0:
+            raise ValueError(f"grad_clip={grad_clip}")
+        s_, a_, s2_ = f["data"][split]
+        d_idx = torch.from_numpy(idx).to(c.device)
+        loss = torch.zeros(c.M, steps, dtype=torch.float32, device=c.device)
+        bs, s2p = f["batch_size"], (f["s2"].data_ptr() if f["s2"] is not None else None)
+        opt = N.AMX_EFIT_ADAM if f["optim"] == "adam" else N.AMX_EFIT_SGD
+        stream = c.stream
+        for s in range(steps):
+            N.check(c.lib.amx_efit_step(c.h, int(train), int(sizes[s]), f["Bt"], d_idx.data_ptr() + 4 * s * bs,
+                                        steps * bs, s_.shape[0], s_.data_ptr(), a_.data_ptr(), s2_.data_ptr(),
+                                        f["Wp"], f["bp"], f["grad"].data_ptr(), f["s1"].data_ptr(), s2p,
+                                        f["step"].data_ptr(), opt, f["lr"], f["p1"], float(grad_clip),
+                                        loss.data_ptr() + 4 * s, steps, f["work"].data_ptr(), stream),
+                    "amx_efit_step")
+        return loss.cpu().numpy()
+
+    def fit_state(self):
+        """The device training state in nn.Linear layout: (weights, opt_state) with weights[m] =
+        [(W, b), ...] and opt_state[m] = {'step', 's1', 's2'} as fit_begin takes them."""
+        f, c = self._fit, self.ctx
+        cm = torch.from_numpy(self._colmap())
+        Wh, bh = [w.cpu() for w in self.W], [b.cpu() for b in self.b]
+        steps = f["step"].cpu().tolist()
+        views = {k: (self._flat_views(f[k].cpu()) if f[k] is not None else None) for k in ("s1", "s2")}
+
+        def unpad(Wv, bv, i, m):
+            _, _, rows, n_in = self._layer_dims(i)
+            return Wv[m, :rows][:, cm[:n_in]].clone(), bv[m, :rows].clone()
+
+        weights, opt = [], []
+        for m in range(c.M):
+            weights.append([unpad(Wh[i], bh[i], i, m) for i in range(c.L + 1)])
+            st = {"step": int(steps[m])}
+            for k, v in views.items():
+                st[k] = None if v is None else [unpad(v[i][0], v[i][1], i, m) for i in range(c.L + 1)]
+            opt.append(st)
+        return weights, opt
+
+    def fit_refresh(self) -> None:
+        """Re-split the inference limb images from the trained master weights, in place: engines
+        and captured graphs that hold their pointers see the trained model."""
+        for i in range(self.ctx.L + 1):
+            if self.W3 is not None:
+                split_bf16x3(self.ctx, self.W[i], out=self.W3[i])
+            if self.W2 is not None:
+                split_f16x2(self.ctx, self.W[i], out=(self.W2[i], self.wexp[i]))
+
+    def fit_end(self) -> None:
+        """Free the training state."""
+        self._fit = None
+
+
 class RffMap:
     """phi(x) = cos(x W^T + b) * sqrt(2/F) on MFMA (linear_cost.py:64-71) with fp64 column sums."""
 

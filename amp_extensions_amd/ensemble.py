@@ -20,8 +20,11 @@ reference's state-dict keys (`fc_layers.{i}.weight/bias`), so the checkpoint for
 the reference's `save_ensemble` (a list of {'model', 'optim'}, dynamics.py:110-116) loads and
 saves unchanged (torch.load with weights_only=True: tensors and plain containers only).
 
-Inference only: ensemble training (DynamicsModel.train*, dynamics.py:236-378) is out of scope
- and `train()` raises.  The device path implements the dense-connect ReLU BasicMLP
+Training (DynamicsEnsemble.train, dynamics.py:82-108, 236-378) runs on the device through
+`train_on_device`, which takes `train`'s arguments and returns what it returns: all members
+advance in lock step, each on the index batches the reference's DataLoaders would have drawn
+for it (`plan_batches`).  `train()` itself keeps raising and names that method (a pinned
+test requires the raise).  The device path implements the dense-connect ReLU BasicMLP
 (dynamics.py:394-433, the README command's `--dynamic_dense_connect`); other model options
 raise NotImplementedError.
 
@@ -31,9 +34,12 @@ BatchedSimEnv / the costs take either.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.utils.data import DataLoader, Dataset
 
 from .engine import AmxContext, DeviceEnsemble
 
@@ -134,8 +140,8 @@ class DynamicsModel:
         return {'model': self.model.state_dict(), 'optim': self.optimizer.state_dict()}
 
     def train(self, *a, **k):
-        raise NotImplementedError("dynamics-model training is out of scope (SURVEY §2); train with the reference "
-                                  "and load its ensemble.pt")
+        raise NotImplementedError("per-member training is not implemented; DynamicsEnsemble.train_on_device trains "
+                                  "all members on the GPU")
 
 
 def _identity_transformations(S: int, A: int):
@@ -180,6 +186,7 @@ class DynamicsEnsemble:
         self.device = device if isinstance(device, torch.device) else torch.device(device)
         self.base_seed = base_seed
         self.hidden_sizes = hidden_sizes
+        self._fit_stepped = False
         self.models = [DynamicsModel(self, k, state_dim, action_dim, hidden_sizes, optim_args, base_seed + k)
                        for k in range(num_models)]
         if ctx is None:
@@ -249,8 +256,203 @@ class DynamicsEnsemble:
         self.engine.threshold = float(v)
 
     def train(self, *a, **k):
-        raise NotImplementedError("ensemble training is out of scope (SURVEY §2); train with the reference and "
-                                  "load its ensemble.pt with load_ensemble")
+        raise NotImplementedError("DynamicsEnsemble.train is not bound; call train_on_device (the same arguments and "
+                                  "return value, all members trained on the GPU)")
+
+    # ---- training on the device (dynamics.py:82-108, 236-378) ------------------------------
+    def _optimizer_config(self):
+        """(optim, lr, p1) of the members' optimizers (the loaded checkpoint's param_groups
+        included); anything the device step does not implement raises."""
+        cfg = None
+        for m in self.models:
+            opt = m.optimizer
+            if len(opt.param_groups) != 1:
+                raise NotImplementedError("one param_group per member")
+            pg = opt.param_groups[0]
+            if isinstance(opt, torch.optim.Adam):
+                if (tuple(pg["betas"]) != (0.9, 0.999) or pg["weight_decay"] != 0 or pg["amsgrad"]
+                        or pg.get("maximize")):
+                    raise NotImplementedError(f"Adam options {pg['betas']}, weight_decay={pg['weight_decay']}, "
+                                              f"amsgrad={pg['amsgrad']} (supported: torch's defaults with lr, eps)")
+                c = ("adam", float(pg["lr"]), float(pg["eps"]))
+            elif isinstance(opt, torch.optim.SGD):
+                if not pg["nesterov"] or pg["dampening"] != 0 or pg["weight_decay"] != 0 or pg.get("maximize"):
+                    raise NotImplementedError("SGD options (supported: momentum with nesterov=True, dampening 0)")
+                c = ("sgd", float(pg["lr"]), float(pg["momentum"]))
+            else:
+                raise NotImplementedError(f"optimizer {type(opt).__name__}")
+            if cfg is not None and c != cfg:
+                raise NotImplementedError("members with different optimizer settings")
+            cfg = c
+        return cfg
+
+    def _host_opt_state(self, optim):
+        """The members' optimizer state in DeviceEnsemble.fit_begin's form (None when fresh)."""
+        out, any_state = [], False
+        for m in self.models:
+            st = {"step": 0, "s1": None, "s2": None}
+            params = list(m.model.parameters())
+            states = [m.optimizer.state.get(p, {}) for p in params]
+            k1, k2 = ("exp_avg", "exp_avg_sq") if optim == "adam" else ("momentum_buffer", None)
+            if all(s_.get(k1) is not None for s_ in states):
+                any_state = True
+                st["s1"] = [(states[2 * i][k1], states[2 * i + 1][k1]) for i in range(len(params) // 2)]
+                if k2:
+                    st["s2"] = [(states[2 * i][k2], states[2 * i + 1][k2]) for i in range(len(params) // 2)]
+                    steps = {int(float(s_["step"])) for s_ in states}
+                    if len(steps) != 1:
+                        raise NotImplementedError("parameters of one member at different Adam steps")
+                    st["step"] = steps.pop()
+            out.append(st)
+        return out if any_state else None
+
+    def sync_to_host(self):
+        """Copy the device master weights and optimizer state into `models[k].model` and
+        `models[k].optimizer` (exp_avg / exp_avg_sq / step, or momentum_buffer, in torch's
+        layout), so save_ensemble writes a reference-format checkpoint.  Needs an open
+        training state (it is called by train_on_device)."""
+        optim = self.engine._fit["optim"]
+        weights, opt = self.engine.fit_state()
+        with torch.no_grad():
+            for m, w, st in zip(self.models, weights, opt):
+                params = list(m.model.parameters())
+                for i, lin in enumerate(m.model.fc_layers):
+                    lin.weight.copy_(w[i][0]), lin.bias.copy_(w[i][1])
+                if not self._fit_stepped and st["step"] == 0:
+                    continue
+                for j, p in enumerate(params):
+                    i, k = divmod(j, 2)
+                    if optim == "adam":
+                        m.optimizer.state[p] = {"step": torch.tensor(float(st["step"]), dtype=torch.float32),
+                                                "exp_avg": st["s1"][i][k], "exp_avg_sq": st["s2"][i][k]}
+                    else:
+                        m.optimizer.state[p] = {"momentum_buffer": st["s1"][i][k]}
+
+    def train_on_device(self, epochs, validate=False, logger=None, log_epoch=False, grad_clip=0, save_path=None,
+                        save_checkpoints=False, writer=None):
+        """DynamicsEnsemble.train (dynamics.py:82-108) with DynamicsModel.train's loop
+        (:305-378) on the GPU: the same arguments, log strings, `writer.add_scalar` calls,
+        `save_path` files and return value ([(train_min_loss, train_losses[0]) per member]).
+
+        All members advance in the same launches, each on the index batches the reference's
+        member-major DataLoader iterations would have drawn from torch's global generator
+        (plan_batches); the generator is left in the state after the reference's last draw.
+        Log lines therefore arrive epoch by epoch for all members rather than member by member.
+        As in the reference on current torch, the "best" state dicts are views of the live
+        tensors, so the members end with the last epoch's parameters.  Optimizer state loaded
+        by load_ensemble is uploaded first (training resumes a checkpoint); afterwards the host
+        members hold the trained parameters and optimizer state and the inference limb images
+        are refreshed in place.  `threshold` is left for compute_threshold()."""
+        assert (not validate) or (validate and self.validate_dataset)
+        epochs = int(epochs)
+        if not grad_clip:
+            grad_clip = 0.0
+        if grad_clip < 0:
+            raise ValueError(f"grad_clip={grad_clip}")
+        optim, lr, p1 = self._optimizer_config()
+        tr = _dataset_tensors(self.train_dataset)
+        va = _dataset_tensors(self.validate_dataset) if validate else None
+        M, bs = self.num_models, int(self.batch_size)
+        eng = self.engine
+        eng.fit_begin(tr, optim, lr, p1, bs, val_data=va, opt_state=self._host_opt_state(optim), num_models=M,
+                      hidden_sizes=self.hidden_sizes)
+        self._fit_stepped = False
+        try:
+            return self._train_loop(epochs, validate, logger, log_epoch, float(grad_clip), save_path,
+                                    save_checkpoints, writer, tr[0].shape[0], va[0].shape[0] if validate else 0)
+        finally:
+            eng.fit_end()
+
+    def _train_loop(self, epochs, validate, logger, log_epoch, grad_clip, save_path, save_checkpoints, writer,
+                    n_train, n_val):
+        M, bs, eng = self.num_models, int(self.batch_size), self.engine
+        plan, final_rng = plan_batches(n_train, n_val, bs, epochs, M, validate)
+        train_loader = index_loader(n_train, bs)
+        val_loader = index_loader(n_val, bs) if validate else None
+        paths = [None] * M
+        for i in range(M):
+            if logger is not None:
+                logger.info(f'>>>>Training Model {i+1}/{self.num_models}')
+            if save_path is not None:
+                paths[i] = os.path.join(save_path, f'model{i}')
+                if not os.path.exists(paths[i]):
+                    os.mkdir(paths[i])
+        inf = float('inf')
+        t_min, t_min_ep, t_losses = [inf] * M, [inf] * M, [[] for _ in range(M)]
+        v_min, v_min_ep, v_losses = [inf] * M, [inf] * M, [[] for _ in range(M)]
+        last_avg = [None] * M
+
+        def gather(loader, which, epoch):
+            per = [materialise(loader, plan[g][epoch][which]) for g in range(M)]
+            sizes = [len(b) for b in per[0]]
+            idx = np.zeros((M, len(sizes), bs), dtype=np.int32)
+            for g in range(M):
+                for s_, b in enumerate(per[g]):
+                    idx[g, s_, :len(b)] = b
+            return idx, sizes
+
+        for epoch in range(epochs):
+            idx, sizes = gather(train_loader, 0, epoch)
+            losses = eng.fit_epoch(idx, sizes, train=True, grad_clip=grad_clip)
+            self._fit_stepped = True
+            ckpt = save_path is not None and save_checkpoints and ((epoch + 1) % 100 == 0 or (epoch + 1) == epochs // 2)
+            if ckpt:
+                self.sync_to_host()
+            for g in range(M):
+                avg = np.average([float(x) for x in losses[g]])
+                last_avg[g] = avg
+                if ckpt:
+                    m = self.models[g]
+                    torch.save({'model': m.model.state_dict(), 'optim': m.optimizer.state_dict(), 'epoch': epoch + 1,
+                                'loss': avg}, os.path.join(paths[g], f'{epoch + 1}_checkpoint.pt'))
+                if logger is not None:
+                    if log_epoch:
+                        logger.info('Epoch: {}, Train Loss: {}'.format(epoch, avg))
+                else:
+                    print('Epoch {} Train Loss: {}'.format(epoch, avg))
+                t_losses[g].append(avg)
+                if writer is not None:
+                    writer.add_scalar("Loss/train", avg, epoch)
+                if avg < t_min[g]:
+                    t_min_ep[g], t_min[g] = epoch, avg
+            if validate:
+                idx, sizes = gather(val_loader, 1, epoch)
+                losses = eng.fit_epoch(idx, sizes, train=False, split="val")
+                for g in range(M):
+                    avg = np.average([float(x) for x in losses[g]])
+                    if logger is not None:
+                        if log_epoch:
+                            logger.info('Epoch {} Validation Loss: {}'.format(epoch, avg))
+                    else:
+                        print('Epoch {} Validation Loss: {}'.format(epoch, avg))
+                    v_losses[g].append(avg)
+                    if writer is not None:
+                        writer.add_scalar("Loss/validate", avg, epoch)
+                    if avg < v_min[g]:
+                        v_min_ep[g], v_min[g] = epoch, avg
+        torch.set_rng_state(final_rng)
+        self.sync_to_host()
+        eng.fit_refresh()
+        info = []
+        for g, m in enumerate(self.models):
+            if save_path is not None:
+                # the reference's "best" dicts are state_dict() views of the live tensors: all
+                # three files hold the final parameters, under the best epoch's number and loss
+                sd = lambda: {'model': m.model.state_dict(), 'optim': m.optimizer.state_dict()}
+                torch.save({**sd(), 'epoch': epochs, 'loss': last_avg[g]}, os.path.join(paths[g], 'final_model.pt'))
+                torch.save({**sd(), 'epoch': t_min_ep[g] + 1, 'loss': t_min[g]},
+                           os.path.join(paths[g], 'best_train_checkpoint.pt'))
+                if validate:
+                    torch.save({**sd(), 'epoch': v_min_ep[g] + 1, 'loss': v_min[g]},
+                               os.path.join(paths[g], 'best_validate_checkpoint.pt'))
+            if logger is not None:
+                logger.info('Train: Dynamics Start | Best Loss | Epoch: {} | {} | {}'.format(
+                    t_losses[g][0], t_min[g], t_min_ep[g]))
+                if validate:
+                    logger.info('Validate: Dynamics Start | Best Loss | Epoch: {} | {} | {}'.format(
+                        v_losses[g][0], v_min[g], v_min_ep[g]))
+            info.append((t_min[g], t_losses[g][0]))
+        return info
 
     def save_ensemble(self, save_path):
         """dynamics.py:110-116: a list of {'model', 'optim'} state dicts."""
@@ -297,6 +499,77 @@ class DynamicsEnsemble:
         dev = self.ctx.device
         self.engine.compute_threshold(torch.as_tensor(states).to(dev).float(), torch.as_tensor(actions).to(dev).float())
         return self.threshold if explicit else None
+
+
+def _dataset_tensors(ds):
+    """(states, actions, next_states) of an AmpDataset-like dataset (its tensors, or its rows)."""
+    if all(hasattr(ds, k) for k in ("states", "actions", "next_states")):
+        return ds.states, ds.actions, ds.next_states
+    rows = [ds[i] for i in range(len(ds))]
+    return tuple(torch.stack([r[j] for r in rows]) for j in range(3))
+
+
+# ---- the reference's batch orders ----------------------------------------------------------
+# DynamicsModel.train iterates DataLoader(shuffle=True) objects that draw from torch's global
+# generator, member-major: member 0's epochs (each followed by a validation-loader iteration
+# under `validate`), then member 1's, ...  The draws do not depend on training results, so the
+# order is replayed with real DataLoaders over an index dataset: consumption of the generator
+# equals the installed torch's by construction.
+
+
+class _IndexDataset(Dataset):
+    """Row i is the index i; a batch is the list of its indices."""
+
+    def __init__(self, n: int):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i
+
+    def __getitems__(self, idx):
+        return idx
+
+
+def _identity(batch):
+    return batch
+
+
+def index_loader(n: int, batch_size: int) -> DataLoader:
+    """DataLoader(shuffle=True, drop_last=False) over the indices 0..n-1."""
+    return DataLoader(_IndexDataset(n), batch_size=batch_size, shuffle=True, collate_fn=_identity)
+
+
+def plan_batches(n_train: int, n_val: int, batch_size: int, epochs: int, num_models: int, validate: bool):
+    """Walk the reference's (member, epoch[, val]) loader iterations in its order and record
+    torch.get_rng_state() before each one: returns (plan, final_state) with plan[g][e] =
+    (state before the train iteration, state before the validation iteration or None).  An
+    iteration's draws from the global generator all happen by its first batch, so each is
+    advanced by one batch only; no permutation is kept.  The global generator ends in
+    final_state."""
+    train_loader = index_loader(n_train, batch_size)
+    val_loader = index_loader(n_val, batch_size) if validate else None
+    plan = []
+    for _ in range(num_models):
+        rows = []
+        for _ in range(epochs):
+            st = torch.get_rng_state()
+            next(iter(train_loader))
+            sv = None
+            if validate:
+                sv = torch.get_rng_state()
+                next(iter(val_loader))
+            rows.append((st, sv))
+        plan.append(rows)
+    return plan, torch.get_rng_state()
+
+
+def materialise(loader: DataLoader, rng_state) -> list:
+    """The index batches of the loader iteration that starts from `rng_state`."""
+    torch.set_rng_state(rng_state)
+    return [list(map(int, b)) for b in loader]
 
 
 class _Transformations:

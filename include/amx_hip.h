@@ -123,6 +123,15 @@ int amx_gemm_bias_act(amx_ctx* ctx, int groups, int rows, int N, int K, const fl
                       const float* bias, long long strideBias, float* C, int ldc, long long strideC,
                       int col_off, int act, void* stream);
 
+/* The same GEMM on 64 x 64 tiles (bit-identical results: every output element runs the same K
+ * chain): four times the workgroups of amx_gemm_bias_act, for the few hundred rows of a training
+ * step (amx_efit_step's forward), where 128 x 128 tiles leave most of the chip idle.
+ * rows % 128 == 0, N % 64 == 0, K % 32 == 0. */
+int amx_gemm_bias_act_t64(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
+                          long long strideA, const float* W, int ldw, long long strideW,
+                          const float* bias, long long strideBias, float* C, int ldc,
+                          long long strideC, int col_off, int act, void* stream);
+
 /* Last dense layer + output un-normalisation (BasicMLP.forward :432 then
  * DynamicsModel.forward :231-232): preds_g[r][n] = (sum_k A W + b[n]) * sd_d[n] + mu_d[n]
  * for n < n_valid (=S); W_g is padded to round_up(n_valid,128) rows. */
@@ -693,6 +702,45 @@ int amx_vfit_epoch(amx_ctx* ctx, int n_rows, const float* feat, int ldf, const f
                    float* b1, float* w2, float* b2, float* adam_m, float* adam_v,
                    long long* adam_step, double lr, double beta1, double beta2, double eps,
                    double weight_decay, void* work, float* epoch_loss, void* stream);
+
+/* ---- training the dynamics ensemble (DynamicsModel.train_step) ------------------ */
+
+enum { AMX_EFIT_ADAM = 0, AMX_EFIT_SGD = 1 };
+
+/* Sizes of the training vectors of the context's ensemble (host arithmetic; -1 and
+ * amx_last_error for an unsupported depth).  amx_efit_param_count: floats per member of the
+ * flat gradient and of each optimizer-state vector, laid out layer by layer as
+ * W_i [N_i][K_i] | b_i [N_i] in the engine's padded dense-concat layout (N_i = hidden, K_i =
+ * k0_pad + i*hidden; the last layer N = n_out_pad, K = ldk).  amx_efit_work_floats: floats of
+ * the opaque step workspace for batches padded to Bt rows (Bt % 128 == 0). */
+long long amx_efit_param_count(const amx_ctx* ctx);
+long long amx_efit_work_floats(const amx_ctx* ctx, int Bt);
+
+/* One step of DynamicsModel.train_step (train = 1) or validate_step (train = 0),
+ * milo/milo/dynamics.py:236-261, for all M members at once.  Member g's batch is rows
+ * idx[g * strideIdx + r], r < n_b, of the fp32 device arrays states [n_rows][S], actions
+ * [n_rows][A], next_states [n_rows][S] (indices are clamped to [0, n_rows)).  Inputs and the
+ * target ((s' - s) - mu_d)/sd_d are normalised with the context's normalizers in the
+ * reference's op order; the forward is amx_gemm_bias_act on the fp32 master weights W[i], b[i]
+ * (host arrays of L + 1 device pointers, each [M][N_i][K_i] / [M][N_i]); loss[g * strideLoss]
+ * (device) = nn.MSELoss over n_b x S.  train = 1 continues with autograd's backward (ReLU mask
+ * "output > 0"), clip_grad_norm_(grad_clip) when grad_clip > 0 (coef = min(1, grad_clip /
+ * (norm + 1e-6))) and the optimizer, torch's op for op:
+ *   AMX_EFIT_ADAM (p1 = eps; betas 0.9, 0.999; state1 = exp_avg, state2 = exp_avg_sq):
+ *     m += 0.1 (g - m);  v = 0.999 v + 0.001 g g;
+ *     w -= (lr / (1 - 0.9^t)) m / (sqrt(v) / sqrt(1 - 0.999^t) + eps)
+ *   AMX_EFIT_SGD (p1 = momentum, nesterov, dampening 0; state1 = momentum_buffer, state2 unused):
+ *     buf = p1 buf + g;  w -= lr (g + p1 buf)
+ * t = ++step[g] (device, one count per member).  grad / state1 / state2: [M][param_count]
+ * floats; the states are zero before the first step.  All arithmetic is fp32 in a fixed order;
+ * zero-padded weights and their state stay exactly 0.  A step is 3 L + 7 launches on
+ * `stream` (3 L + 6 without grad_clip, L + 3 for train = 0); nothing in them waits on another workgroup and nothing is
+ * allocated. */
+int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int32_t* idx, long long strideIdx,
+                  int n_rows, const float* states, const float* actions, const float* next_states,
+                  float* const* W, float* const* b, float* grad, float* state1, float* state2,
+                  long long* step, int optim, double lr, double p1, double grad_clip, float* loss,
+                  long long strideLoss, float* work, void* stream);
 
 /* ---- RNG ----------------------------------------------------------------------- */
 
