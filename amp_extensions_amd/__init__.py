@@ -15,7 +15,7 @@ from .humanoid import TerminationConfig  # noqa: F401
 __all__ = [
     "AmxContext", "DeviceEnsemble", "RffMap", "RolloutEngine", "RBFLinearCost", "GAILCost", "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
-    "DeviceNPG",
+    "DeviceNPG", "AgentReplayBuffer",
 ]
 
 
@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in ("RBFLinearCost", "GAILCost"):
         from . import costs
         return getattr(costs, name)
+    if name == "AgentReplayBuffer":
+        from .datasets import AgentReplayBuffer
+        return AgentReplayBuffer
     if name == "DevicePolicy":
         from .policy import DevicePolicy
         return DevicePolicy

@@ -146,6 +146,13 @@ SIGNATURES = {
     "amx_efit_work_floats": (c_ll, [vp, c_int]),
     "amx_efit_step": (c_int, [vp, c_int, c_int, c_int, vp, c_ll, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int,
                               c_dbl, c_dbl, c_dbl, vp, c_ll, vp, vp]),
+    "amx_gemm_nn_f32": (c_int, [vp, c_int, c_int, c_int, vp, c_int, vp, c_int, vp, c_int, vp, c_int, c_int, vp]),
+    "amx_gemm_tn_f32": (c_int, [vp, c_int, c_int, c_int, vp, c_int, vp, c_int, vp, c_int, vp, c_int, vp, c_int, vp]),
+    "amx_dfit_param_count": (c_ll, [c_int, c_int, c_int]),
+    "amx_dfit_work_floats": (c_ll, [c_int, c_int, c_int, c_int]),
+    "amx_dfit_step": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_int, c_int, c_int, c_int,
+                              c_int, vp, vp, vp, c_ll, c_int, vp, c_ll, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                              vp, vp]),
     "amx_philox":(c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
     "amx_mt_seed": (c_int, [vp, c_int, vp, vp, c_int]),
     "amx_mt_policy_noise": (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_ll, c_ll]),
@@ -159,6 +166,7 @@ AMX_ACT_NONE, AMX_ACT_RELU = 0, 1
 AMX_IN_F64, AMX_IN_F32 = 0, 1
 AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
 AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1
+AMX_DFIT_SGD, AMX_DFIT_ADAM = 0, 1
 
 
 class AmxNativeError(RuntimeError):

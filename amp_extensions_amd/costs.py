@@ -1,8 +1,8 @@
 """Device-backed drop-ins for the reference cost objects.
 
 * `RBFLinearCost` — milo/milo/linear_cost.py:6-152 (MILO RFF MMD cost + pessimism bonus)
-* `GAILCost`      — milo/milo/gail_cost.py:44-279, inference surface (AMP least-squares
-                    discriminator reward + bonus); discriminator training is out of scope.
+* `GAILCost`      — milo/milo/gail_cost.py:44-279: the AMP discriminator's reward + bonus and
+                    its training step (update_disc, compute_chi2_distance) on the device.
 
 Initialisation reproduces the reference's torch-CPU RNG stream exactly (seed, bandwidth
 draw, nn.Linear construction order), so the same seed yields the same W, b, bandwidth and
@@ -316,8 +316,36 @@ class RBFLinearCost:
                                   "cost": cost.view(-1, 1)}
 
 
+def plan_disc_batch(n_rb: int, n_expert: int, bs: int, sample_rb: bool):
+    """The index draws of one GAILCost.update_disc (gail_cost.py:169-176) from numpy's global
+    generator, in the reference's order: with sample_rb (mb_ss=None) the replay buffer's
+    np.random.randint(0, n_rb, bs) first (datasets.py:101), then the expert's
+    np.random.randint(0, n_expert, bs) (gail_cost.py:95).  Returns (agent rows in the buffer's
+    logical order or None, expert rows)."""
+    idx_m = np.random.randint(0, n_rb, bs) if sample_rb else None
+    return idx_m, np.random.randint(0, n_expert, bs)
+
+
+class _Disc(nn.Module):
+    """Host mirror of the discriminator with the reference's state_dict keys (net.0, net.2, net.4)."""
+
+    def __init__(self, layers):
+        super().__init__()
+        mods = []
+        for i, lin in enumerate(layers):
+            mods += ([nn.ReLU(inplace=True)] if i else []) + [lin]
+        self.net = nn.Sequential(*mods)
+
+    def forward(self, obs):
+        return self.net(obs)
+
+
 class GAILCost:
-    """AMP/GAIL least-squares discriminator cost, inference surface (gail_cost.py:44-279)."""
+    """AMP/GAIL discriminator cost (gail_cost.py:44-279): rewards, bonus costs, and the
+    discriminator's training (update_disc, compute_chi2_distance) on the device."""
+
+    DISC_BATCH = 256      # rows update_disc samples when mb_ss is None (gail_cost.py:173)
+    CHI2_CHUNK = 16384    # rows per inference pass of compute_chi2_distance
 
     def __init__(self, expert_data: torch.Tensor, agent_rb=None, feature_dim: int = 1, hidden_dims=(1024, 512),
                  input_type: str = "ss", scaling_coef: float = 0.5, reg_coef: float = 0.05, lambda_b: float = 0.5,
@@ -347,6 +375,21 @@ class GAILCost:
             else:
                 nn.init.xavier_uniform_(lin.weight.data)
         self.weights = [(l.weight.data.clone(), l.bias.data.clone()) for l in layers]
+        # training (gail_cost.py:66-92): no RNG is drawn below
+        self.online_rb = agent_rb
+        self.n_expert_samples = expert_data.size(0)
+        self.feature_dim = feature_dim
+        self.scaling_coef, self.reg_coef, self.grad_lambda = float(scaling_coef), float(reg_coef), float(grad_lambda)
+        opt_args = {"lr": 0.00001, "momentum": 0.9} if disc_opt_args is None else dict(disc_opt_args)
+        self._opt_kind = "sgd" if disc_opt == "sgd" else "adam"
+        self._opt_lr = float(opt_args["lr"])
+        self._opt_p1 = float(opt_args["momentum"]) if self._opt_kind == "sgd" else 1e-8
+        self._layers = layers
+        self._disc = _Disc(layers)   # host mirror, synced from the device copy when that is newer
+        self._disc_opt = None
+        self._train = None           # device optimizer state and workspaces (first update_disc)
+        self._steps = 0              # optimizer steps taken (the device's count)
+        self._expert_dev = None
         if ctx is None:
             S = self.input_dim // 2 if input_type == "ss" else self.input_dim
             ctx = AmxContext(S, 1, n_models=1, hidden=128, n_hidden=0, feat_dim=128, device=device)
@@ -355,9 +398,16 @@ class GAILCost:
             raise ValueError(f"gemm must be 'f16x3', 'bf16x6' or 'f32', got {gemm!r}")
         self.gemm = gemm
         self.load_weights(self.weights)
+        self._dev_newer = False
 
-    def load_weights(self, weights) -> None:
-        """Upload discriminator weights (e.g. after an out-of-scope training step)."""
+    def load_weights(self, weights, optimizer=None) -> None:
+        """Upload discriminator weights: a list of (W, b) pairs or a `disc.state_dict()`.
+        `optimizer` (a `disc_opt.state_dict()`) also seeds the device optimizer state, to
+        resume training from a checkpoint; without it the optimizer starts afresh."""
+        if isinstance(weights, dict):
+            n = len(weights) // 2
+            weights = [(weights[f"net.{2 * i}.weight"], weights[f"net.{2 * i}.bias"]) for i in range(n)]
+        opt = None if optimizer is None else self._parse_optimizer(optimizer, weights)
         dev = self.ctx.device
         self.Kin = round_up(self.input_dim, 32)
         self.dev_layers = []
@@ -385,6 +435,267 @@ class GAILCost:
         self.b3 = float(b3.float().cpu().view(-1)[0])
         self.h_last = k_pad
         self._ws = {}
+        self._train, self._steps, self._disc_opt = None, 0, None
+        self._dev_newer = True   # the host mirror follows the uploaded weights
+        if opt is not None:
+            self._opt_kind, self._opt_lr, self._opt_p1, self._steps, state = opt
+            t = self._train_state()
+            t.step.fill_(self._steps)
+            for vec, rows in zip((t.s1, t.s2), state):
+                if vec is not None and rows is not None:
+                    for (off, shape, valid), v in zip(self._param_slices(), rows):
+                        vec[off:off + shape[0] * shape[1]].view(shape)[:valid[0], :valid[1]] = \
+                            v.detach().float().reshape(valid).to(dev)
+
+    # ---- training: update_disc / compute_chi2_distance (gail_cost.py:94-228) ----------------
+
+    _SUPPORTED = ("two hidden layers, trained by torch.optim.SGD(lr, momentum) without Nesterov, dampening or "
+                  "weight decay, or by torch.optim.Adam(lr) with betas (0.9, 0.999), no weight decay, no amsgrad")
+
+    def _check_trainable(self) -> None:
+        if len(self._layers) != 3:
+            raise NotImplementedError(f"update_disc on the device supports {self._SUPPORTED}; this discriminator "
+                                      f"has {len(self._layers) - 1} hidden layer(s)")
+
+    def _parse_optimizer(self, sd, weights):
+        """(kind, lr, p1, steps, (state1 rows, state2 rows)) of a torch optimizer state_dict over
+        the six tensors; refuses what amx_dfit_step does not cover, before anything is allocated."""
+        if len(weights) != 3:
+            raise NotImplementedError(f"update_disc on the device supports {self._SUPPORTED}; the weights given "
+                                      f"have {len(weights) - 1} hidden layer(s)")
+        groups = sd["param_groups"]
+        g = groups[0]
+        if len(groups) != 1 or len(g["params"]) != 6:
+            raise NotImplementedError(f"one parameter group over the six tensors is supported ({self._SUPPORTED})")
+        if "momentum" in g:
+            if g.get("nesterov") or g.get("dampening", 0) != 0 or g.get("weight_decay", 0) != 0 or g.get("maximize"):
+                raise NotImplementedError(f"unsupported SGD options; supported: {self._SUPPORTED}")
+            kind, p1 = "sgd", float(g["momentum"])
+        else:
+            if tuple(g["betas"]) != (0.9, 0.999) or g.get("weight_decay", 0) != 0 or g.get("amsgrad") or \
+                    g.get("maximize"):
+                raise NotImplementedError(f"unsupported Adam options; supported: {self._SUPPORTED}")
+            kind, p1 = "adam", float(g["eps"])
+        st = [sd["state"].get(p) for p in g["params"]]
+        steps, s1, s2 = 0, None, None
+        if all(s for s in st):
+            if kind == "sgd":
+                if all(s.get("momentum_buffer") is not None for s in st):
+                    s1, steps = [s["momentum_buffer"] for s in st], 1   # SGD keeps no count
+            else:
+                s1, s2 = [s["exp_avg"] for s in st], [s["exp_avg_sq"] for s in st]
+                steps = int(float(st[0]["step"]))
+        return kind, float(g["lr"]), p1, steps, (s1, s2)
+
+    def _param_slices(self):
+        """(offset, padded [rows, cols], valid [rows, cols]) of W0, b0, W1, b1, w2, b2 in the flat
+        optimizer-state vectors (amx_dfit_param_count's layout)."""
+        (_, _, H0p, Dp, _), (_, _, H1p, _, _) = self.dev_layers
+        h0, h1 = self._layers[0].out_features, self._layers[1].out_features
+        shapes = [((H0p, Dp), (h0, self.input_dim)), ((1, H0p), (1, h0)), ((H1p, H0p), (h1, h0)), ((1, H1p), (1, h1)),
+                  ((1, H1p), (1, h1)), ((1, 4), (1, 1))]
+        out, off = [], 0
+        for shape, valid in shapes:
+            out.append((off, shape, valid))
+            off += shape[0] * shape[1]
+        return out
+
+    def _train_state(self):
+        """Device optimizer state beside the master weights (allocated once)."""
+        if self._train is not None:
+            return self._train
+        self._check_trainable()
+        from types import SimpleNamespace
+        c, dev = self.ctx, self.ctx.device
+        (_, _, H0p, Dp, _), (_, _, H1p, _, _) = self.dev_layers
+        P = c.lib.amx_dfit_param_count(Dp, H0p, H1p)
+        if P < 0:
+            raise N.AmxNativeError("amx_dfit_param_count: " + c.lib.amx_last_error().decode())
+        t = SimpleNamespace(P=P, work={}, idx={})
+        t.s1 = torch.zeros(P, dtype=torch.float32, device=dev)
+        t.s2 = torch.zeros(P, dtype=torch.float32, device=dev) if self._opt_kind == "adam" else None
+        t.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        # one read-back per step: the 8 metrics (fp64) and, behind them, the master b2 [4] (fp32)
+        t.rbuf = torch.zeros(10, dtype=torch.float64, device=dev)
+        t.b2 = t.rbuf[8:].view(torch.float32)
+        t.b2[0] = self.b3
+        self._train = t
+        return t
+
+    def _expert_rows(self) -> torch.Tensor:
+        if self._expert_dev is None:
+            self._expert_dev = self.expert_data.detach().to(self.ctx.device, torch.float32).contiguous()
+        return self._expert_dev
+
+    def sample_from_expert_data(self, batch_size: int):
+        """gail_cost.py:94-97."""
+        idxs = np.random.randint(0, self.n_expert_samples, batch_size)
+        return self.expert_data[idxs]
+
+    def sample_from_online_buffer(self, batch_size: int):
+        """gail_cost.py:99-102."""
+        assert self.online_rb is not None, 'Cannot sample from nonexistent buffer.'
+        return self.online_rb.sample(batch_size)
+
+    def update_disc(self, mb_ss):
+        """gail_cost.py:169-204 in one chain of launches (amx_dfit_step) on the fp32 master
+        weights, then the refresh of the inference copies; one host synchronisation, the
+        read-back of the metrics.  The index draws come from numpy's global generator in the
+        reference's order (plan_disc_batch); with mb_ss=None the agent rows are read from the
+        replay ring in place."""
+        from .datasets import AgentReplayBuffer, ring_rows
+        self._check_trainable()
+        c, dev = self.ctx, self.ctx.device
+        rb = None
+        if mb_ss is None:
+            assert self.online_rb is not None, 'need to sample from online buffer to get agent data!'
+            rb = self.online_rb
+            if not (isinstance(rb, AgentReplayBuffer) and rb.device == dev):
+                mb_ss, rb = self.sample_from_online_buffer(self.DISC_BATCH), None
+        if rb is not None:
+            if len(rb) == 0:
+                raise Exception('Not possible to sample from empty dataset.')
+            if rb.ring.shape[1] != self.input_dim:
+                raise ValueError(f"the replay buffer's rows have {rb.ring.shape[1]} entries, the discriminator's "
+                                 f"input {self.input_dim}")
+            bs = self.DISC_BATCH
+            idx_m, idx_e = plan_disc_batch(len(rb), self.n_expert_samples, bs, True)
+            idx_m = ring_rows(rb.head, rb.n, rb.max_size, idx_m)
+            agent, n_agent = rb.ring, rb.max_size
+        else:
+            bs = mb_ss.size(0)
+            _, idx_e = plan_disc_batch(0, self.n_expert_samples, bs, False)
+            idx_m = None
+            agent, n_agent = mb_ss.detach().to(dev, torch.float32).contiguous(), bs
+            if agent.dim() != 2 or agent.shape[1] != self.input_dim:
+                raise ValueError(f"mb_ss must be [n, {self.input_dim}], got {tuple(agent.shape)}")
+        t = self._train_state()
+        (W0, b0, H0p, Dp, _), (W1, b1, H1p, _, _) = self.dev_layers
+        Bt = round_up(bs, 64)
+        work = t.work.get(Bt)
+        if work is None:
+            nw = c.lib.amx_dfit_work_floats(Dp, H0p, H1p, Bt)
+            if nw < 0:
+                raise N.AmxNativeError("amx_dfit_work_floats: " + c.lib.amx_last_error().decode())
+            work = t.work[Bt] = torch.empty(nw, dtype=torch.float32, device=dev)
+            t.idx[Bt] = (torch.zeros(2, Bt, dtype=torch.int32).pin_memory(),
+                         torch.zeros(2, Bt, dtype=torch.int32, device=dev))
+        host_idx, dev_idx = t.idx[Bt]
+        host_idx[0, :bs] = torch.from_numpy(idx_e.astype(np.int32))
+        if idx_m is not None:
+            host_idx[1, :bs] = torch.from_numpy(idx_m.astype(np.int32))
+        dev_idx.copy_(host_idx, non_blocking=True)
+        expert = self._expert_rows()
+        adam = self._opt_kind == "adam"
+        N.check(c.lib.amx_dfit_step(c.h, self.loss_code, N.AMX_DFIT_ADAM if adam else N.AMX_DFIT_SGD, self._opt_lr,
+                                    self._opt_p1, self.scaling_coef, self.reg_coef, self.grad_lambda, bs, Bt,
+                                    self.input_dim, Dp, H0p, H1p, dev_idx[0].data_ptr(),
+                                    None if idx_m is None else dev_idx[1].data_ptr(), expert.data_ptr(),
+                                    expert.stride(0), self.n_expert_samples, agent.data_ptr(), agent.stride(0),
+                                    n_agent, W0.data_ptr(), b0.data_ptr(), W1.data_ptr(), b1.data_ptr(),
+                                    self.w3.data_ptr(), t.b2.data_ptr(), t.s1.data_ptr(), N.ptr(t.s2),
+                                    t.step.data_ptr(), work.data_ptr(), t.rbuf.data_ptr(), c.stream), "amx_dfit_step")
+        # the inference copies of the selected gemm follow the master weights (w3 is the master itself)
+        for (Wd, _, _, _, W3) in self.dev_layers:
+            if self.gemm == "f16x3":
+                split_f16x2(c, Wd.unsqueeze(0), out=(W3[0].unsqueeze(0), W3[1].unsqueeze(0)))
+            elif self.gemm == "bf16x6":
+                split_bf16x3(c, Wd.unsqueeze(0), out=W3.unsqueeze(0))
+        host = t.rbuf.cpu()   # the step's one host synchronisation
+        self.b3 = float(host[8:].view(torch.float32)[0])
+        self._steps += 1
+        self._dev_newer = True
+        m = host[:8].tolist()
+        metrics = {'expert_disc_loss': m[0], 'model_based_disc_loss': m[1], 'gradient_penalty': m[2],
+                   'regularizer_loss': m[3], 'total_disc_loss': m[4]}
+        if self.loss_code == N.AMX_DISC_LEAST_SQUARES:
+            metrics.update({'expert_acc': torch.tensor(m[5], dtype=torch.float32),
+                            'mb_acc': torch.tensor(m[6], dtype=torch.float32)})
+        return metrics
+
+    def _sq_sum(self, table: torch.Tensor, idx: torch.Tensor | None, n: int, shift: float) -> torch.Tensor:
+        """fp64 device sum of (D(row) + shift)^2 over rows idx (or the first n rows) of `table`,
+        through the inference path in chunks."""
+        acc = torch.zeros((), dtype=torch.float64, device=self.ctx.device)
+        for lo in range(0, n, self.CHI2_CHUNK):
+            hi = min(lo + self.CHI2_CHUNK, n)
+            rows = table[lo:hi] if idx is None else table[idx[lo:hi]]
+            xp, rows_p, k = self._pad(rows)
+            logits = torch.empty(k, dtype=torch.float32, device=self.ctx.device)
+            self.rewards_from_input(xp, rows_p, k, None, logits=logits)
+            acc += ((logits.double() + shift) ** 2).sum()
+        return acc
+
+    @torch.no_grad()
+    def compute_chi2_distance(self) -> float:
+        """gail_cost.py:206-228: scaling_coef mean (D(expert) - 1)^2 + (1 - scaling_coef) mean
+        (D(agent) + 1)^2 over the whole of the smaller set and as many sampled rows of the
+        larger one (np.random.randint from the global generator, as the reference)."""
+        from .datasets import AgentReplayBuffer, ring_rows
+        assert self.online_rb is not None, 'Cannot compute divergence if there is no agent data.'
+        rb, dev, ne = self.online_rb, self.ctx.device, self.n_expert_samples
+        n = len(rb)
+        if n == 0:
+            raise Exception('Not possible to sample from empty dataset.')
+        ring = isinstance(rb, AgentReplayBuffer) and rb.device == dev
+        table = rb.ring if ring else torch.cat([rb.states, rb.next_states], dim=-1).to(dev, torch.float32)
+        if n < ne:
+            e_idx = torch.from_numpy(np.random.randint(0, ne, size=n)).to(dev)
+            a_idx, cnt = None, n    # every held row once: the ring's physical rows [0, n)
+        else:
+            e_idx, cnt = None, ne
+            a = np.random.randint(0, n, size=ne)
+            a_idx = torch.from_numpy(ring_rows(rb.head, rb.n, rb.max_size, a) if ring else a).to(dev)
+        se = self._sq_sum(self._expert_rows(), e_idx, cnt, -1.0)
+        sa = self._sq_sum(table, a_idx, cnt, 1.0)
+        return float(((self.scaling_coef * se + (1.0 - self.scaling_coef) * sa) / cnt).item())
+
+    def _make_opt(self):
+        if self._opt_kind == "sgd":
+            return torch.optim.SGD(self._disc.parameters(), lr=self._opt_lr, momentum=self._opt_p1)
+        return torch.optim.Adam(self._disc.parameters(), lr=self._opt_lr, eps=self._opt_p1)
+
+    def sync_to_host(self) -> None:
+        """Bring the host mirrors (`disc`, `disc_opt`) up to the device copy."""
+        if self._disc_opt is None:
+            self._disc_opt = self._make_opt()
+        if not self._dev_newer:
+            return
+        with torch.no_grad():
+            k_in = self.input_dim
+            for lin, (Wd, bp, _, _, _) in zip(self._layers[:-1], self.dev_layers):
+                lin.weight.copy_(Wd[:lin.out_features, :k_in].cpu())
+                lin.bias.copy_(bp[:lin.out_features].cpu())
+                k_in = lin.out_features
+            self._layers[-1].weight.copy_(self.w3[:k_in].view(1, -1).cpu())
+            self._layers[-1].bias.fill_(self.b3)
+        self._disc_opt = self._make_opt()
+        t = self._train
+        if t is not None and self._steps > 0:
+            s1, s2 = t.s1.cpu(), (None if t.s2 is None else t.s2.cpu())
+            for p, (off, shape, valid) in zip(self._disc.parameters(), self._param_slices()):
+                def cut(v, off=off, shape=shape, valid=valid, p=p):
+                    return v[off:off + shape[0] * shape[1]].view(shape)[:valid[0], :valid[1]].reshape(p.shape).clone()
+                if self._opt_kind == "sgd":
+                    self._disc_opt.state[p] = {"momentum_buffer": cut(s1)}
+                else:
+                    self._disc_opt.state[p] = {"step": torch.tensor(float(self._steps)), "exp_avg": cut(s1),
+                                               "exp_avg_sq": cut(s2)}
+        self._dev_newer = False
+
+    @property
+    def disc(self):
+        """The discriminator as a torch module with the reference's state_dict keys (net.0.weight
+        .. net.4.bias), synced from the device copy when that is newer."""
+        self.sync_to_host()
+        return self._disc
+
+    @property
+    def disc_opt(self):
+        """A torch.optim.SGD / Adam over `disc`'s parameters holding the device optimizer's
+        state, so the reference's save_checkpoint (milo/utils.py:38-44) works as written."""
+        self.sync_to_host()
+        return self._disc_opt
 
     def _hidden(self, x_pad: torch.Tensor, rows: int, row_exp: torch.Tensor | None = None) -> torch.Tensor:
         """Hidden layers over `rows` padded input rows.  f16x3: `row_exp` [rows] int32 = the

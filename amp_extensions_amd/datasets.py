@@ -1,7 +1,9 @@
-"""Normalizer contract of the offline dataset (milo/milo/datasets.py:6-49) and the on-disk
-trajectory databases the offline/expert sets are read from (milo/milo/utils.py:222-305)."""
+"""Normalizer contract of the offline dataset (milo/milo/datasets.py:6-49), the agent replay
+buffer of the AMP loop (datasets.py:51-104) as a device ring, and the on-disk trajectory
+databases the offline/expert sets are read from (milo/milo/utils.py:222-305)."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -34,6 +36,86 @@ class AmpDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         return self.states[idx].float(), self.actions[idx].float(), self.next_states[idx].float()
+
+
+def ring_rows(head: int, n: int, cap: int, idx) -> np.ndarray:
+    """Physical ring rows (int64) of the logical rows `idx` of a ring that holds n <= cap rows,
+    the oldest at physical row `head`: logical row i is physical row (head + i) mod cap."""
+    idx = np.asarray(idx, dtype=np.int64)
+    if idx.size and (idx.min() < -n or idx.max() >= n):
+        raise IndexError(f"row index out of range for {n} rows")
+    return (head + np.where(idx < 0, idx + n, idx)) % cap
+
+
+class AgentReplayBuffer(torch.utils.data.Dataset):
+    """AgentReplayBuffer (datasets.py:51-104) as one device ring [max_size][2 S] of fp32 rows
+    [s, s'] (allocated at the first add, when S is known): `add` appends, host or device
+    tensors alike, and keeps the last max_size rows without copying the rest; `sample` draws
+    np.random.randint(0, len, batch_size) from numpy's global generator over the logical
+    (oldest first) order and returns cat([s, s'], -1), as the reference."""
+
+    def __init__(self, states=None, next_states=None, device="cuda", max_size=100000):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_size = int(max_size)
+        self.ring = None   # [max_size][2 S] fp32 on self.device
+        self.head = 0      # physical row of logical row 0
+        self.n = 0         # rows held
+        self.S = None
+        if states is not None:
+            self.add(states, next_states)
+
+    def __len__(self):
+        return self.n
+
+    def _logical(self, idx=None) -> torch.Tensor:
+        i = np.arange(self.n) if idx is None else idx
+        rows = torch.from_numpy(ring_rows(self.head, self.n, self.max_size, i)).to(self.device)
+        return self.ring[rows]
+
+    @property
+    def states(self):
+        """The held states in logical order (a copy; None when empty, as the reference)."""
+        return None if self.n == 0 else self._logical()[:, :self.S]
+
+    @property
+    def next_states(self):
+        return None if self.n == 0 else self._logical()[:, self.S:]
+
+    def __getitem__(self, idx):
+        if self.n == 0:
+            raise Exception('Not possible to select from empty dataset.')
+        i = np.arange(self.n)[idx.cpu().numpy() if torch.is_tensor(idx) else idx]
+        rows = self._logical(np.atleast_1d(i))
+        rows = rows[0] if np.ndim(i) == 0 else rows
+        return rows[..., :self.S], rows[..., self.S:]
+
+    def add(self, states, next_states):
+        rows = torch.cat([states.to(self.device, torch.float32), next_states.to(self.device, torch.float32)], dim=1)
+        m, cap = rows.shape[0], self.max_size
+        if self.ring is None:
+            self.S = states.shape[1]
+            self.ring = torch.zeros(cap, 2 * self.S, dtype=torch.float32, device=self.device)
+        elif rows.shape[1] != 2 * self.S:
+            raise ValueError(f"rows of {rows.shape[1] // 2} state entries added to a buffer of {self.S}")
+        if m >= cap:   # only the last max_size rows survive
+            self.ring.copy_(rows[m - cap:])
+            self.head, self.n = 0, cap
+            return
+        start = (self.head + self.n) % cap
+        first = min(m, cap - start)
+        self.ring[start:start + first] = rows[:first]
+        if m > first:
+            self.ring[:m - first] = rows[first:]
+        self.head = (self.head + max(0, self.n + m - cap)) % cap
+        self.n = min(self.n + m, cap)
+
+    def sample(self, batch_size):
+        if self.n == 0:
+            raise Exception('Not possible to sample from empty dataset.')
+        idxs = np.random.randint(0, self.n, batch_size)
+        return self._logical(idxs)
 
 
 # ---- on-disk trajectory databases (milo/milo/utils.py:222-305) ----------------------------

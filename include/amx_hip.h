@@ -742,6 +742,64 @@ int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int32_t* idx, 
                   long long* step, int optim, double lr, double p1, double grad_clip, float* loss,
                   long long strideLoss, float* work, void* stream);
 
+/* ---- training the AMP/GAIL discriminator (GAILCost.update_disc) ------------------ */
+
+enum { AMX_DFIT_SGD = 0, AMX_DFIT_ADAM = 1 };
+
+/* General fp32 products on v_mfma_f32_32x32x2_f32 (64 x 64 tiles, LDS-staged operands, one
+ * fp32 FMA chain per output element in ascending k), the backward products autograd runs for
+ * a Linear layer (milo/milo/gail_cost.py:191, total_loss.backward()).  Plain row-major
+ * operands with leading dimensions (multiples of 4 floats, 16-byte aligned bases).
+ *   amx_gemm_nn_f32: C [M][N] = A [M][K] B [K][N]          (dX = dZ W with B = W [out][in])
+ *   amx_gemm_tn_f32: C [M][N] = A^T B, A [R][M], B [R][N]  (dW = dZ^T X), and with colsum != NULL
+ *                    colsum[m] = sum_{r < colsum_rows} A[r][m]  (db over a row prefix)
+ * M % 64 == 0, N % 4 == 0, the reduction length (K, R) % 32 == 0.  mask != NULL applies the
+ * epilogue C[r][n] = mask[r'][n] > 0 ? C[r][n] : 0 with r' = r % mask_mod (mask_mod = 0 and
+ * amx_gemm_tn_f32: r' = r): the ReLU backward by the layer's output. */
+int amx_gemm_nn_f32(amx_ctx* ctx, int M, int N, int K, const float* A, int lda, const float* B,
+                    int ldb, float* C, int ldc, const float* mask, int ldm, int mask_mod,
+                    void* stream);
+int amx_gemm_tn_f32(amx_ctx* ctx, int R, int M, int N, const float* A, int lda, const float* B,
+                    int ldb, float* C, int ldc, const float* mask, int ldm, float* colsum,
+                    int colsum_rows, void* stream);
+
+/* Sizes for amx_dfit_step (host arithmetic; -1 and amx_last_error for unsupported shapes; Dp %
+ * 32 == 0, H0p and H1p % 128 == 0, Bt % 64 == 0).  amx_dfit_param_count: floats of each
+ * optimizer-state vector, laid out W0 [H0p][Dp] | b0 [H0p] | W1 [H1p][H0p] | b1 [H1p] | w2
+ * [H1p] | b2 [4].  amx_dfit_work_floats: floats of the opaque step workspace. */
+long long amx_dfit_param_count(int Dp, int H0p, int H1p);
+long long amx_dfit_work_floats(int Dp, int H0p, int H1p, int Bt);
+
+/* One step of GAILCost.update_disc (milo/milo/gail_cost.py:169-204 with the losses of :104-140,
+ * regularizer_loss :142-146 and expert_grad_pen :148-167) for the discriminator x -> relu(x
+ * W0^T + b0) -> relu(. W1^T + b1) -> . w2 + b2 on the zero-padded fp32 device tensors W0
+ * [H0p][Dp], b0 [H0p], W1 [H1p][H0p], b1 [H1p], w2 [H1p], b2 [4] (b2[1..3] zero).  The expert
+ * batch is rows idx_e[r], r < bs, of expert [n_expert][ld_expert]; the agent batch rows idx_m[r]
+ * of agent [n_agent][ld_agent] (a replay ring's physical rows), or rows 0 .. bs-1 with idx_m =
+ * NULL (an uploaded batch); D valid columns each, indices clamped.  Bt >= bs is the padded
+ * batch.  loss_type AMX_DISC_LEAST_SQUARES: e = mean (out_e - 1)^2, m = mean (out_m + 1)^2;
+ * AMX_DISC_LOG_LIKELIHOOD: e = -mean log sigmoid(out_e), m = -mean log(1 - sigmoid(out_m)).
+ * The gradient is that of scaling_coef e + (1 - scaling_coef) m + grad_lambda/2 mean_e |d out /
+ * d x|_2 (the plain norm; rows of zero norm contribute no gradient, as torch's norm backward);
+ * the regularizer reg_coef sum 1/2 |W|^2 over W0, W1, w2 is logged only (the reference detaches
+ * it).  optim AMX_DFIT_SGD (p1 = momentum; no Nesterov, dampening or weight decay; state1 =
+ * momentum_buffer, state2 unused): buf = p1 buf + g; w -= lr buf.  AMX_DFIT_ADAM (p1 = eps,
+ * betas 0.9 / 0.999; state1 = exp_avg, state2 = exp_avg_sq), torch's single-tensor path as
+ * amx_efit_step.  t = ++step[0] (device).  state1 / state2: amx_dfit_param_count floats, zero
+ * before the first step.  metrics (device, 8 doubles) = expert loss, agent loss, gradient
+ * penalty (x grad_lambda), regularizer (x reg_coef, of the weights before the step), total,
+ * expert accuracy mean(out_e > 0), agent accuracy mean(out_m < 0), t.  All arithmetic is fp32
+ * (the metrics' sums fp64) in a fixed order: a step is bit-reproducible; zero-padded weights
+ * and their state stay exactly 0.  15 launches on `stream`; nothing in them waits on another
+ * workgroup and nothing is allocated. */
+int amx_dfit_step(amx_ctx* ctx, int loss_type, int optim, double lr, double p1, double scaling_coef,
+                  double reg_coef, double grad_lambda, int bs, int Bt, int D, int Dp, int H0p,
+                  int H1p, const int32_t* idx_e, const int32_t* idx_m, const float* expert,
+                  long long ld_expert, int n_expert, const float* agent, long long ld_agent,
+                  int n_agent, float* W0, float* b0, float* W1, float* b1, float* w2, float* b2,
+                  float* state1, float* state2, long long* step, float* work, double* metrics,
+                  void* stream);
+
 /* ---- RNG ----------------------------------------------------------------------- */
 
 /* Philox4x32-10 block for (key = seed, counter = {ctr0, ctr1, ctr2, ctr3}), written
