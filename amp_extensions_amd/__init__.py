@@ -6,7 +6,8 @@ reward and the humanoid3d fall/horizon termination, as hand-written HIP kernels 
 gfx950 behind a C ABI (include/amx_hip.h, libamx_hip.so) and the reference's Python
 surfaces (SimEnv, sample_points, RBFLinearCost, GAILCost, DynamicsEnsemble), plus the
 sampler's consumers: returns, MLP value baseline (prediction and the mini-batch Adam fit) and
-GAE (mjrl process_samples, MLPBaseline) and the NPG policy update (mjrl npg_cg).
+GAE (mjrl process_samples, MLPBaseline), the NPG policy update (mjrl npg_cg) and the
+behaviour-cloning warm start (mjrl BC).
 
 The native library is loaded on first use; there is no CPU fallback.
 """
@@ -15,7 +16,7 @@ from .humanoid import TerminationConfig  # noqa: F401
 __all__ = [
     "AmxContext", "DeviceEnsemble", "RffMap", "RolloutEngine", "RBFLinearCost", "GAILCost", "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
-    "DeviceNPG", "AgentReplayBuffer",
+    "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
 ]
 
 
@@ -44,6 +45,9 @@ def __getattr__(name):
     if name == "DeviceNPG":
         from .npg import DeviceNPG
         return DeviceNPG
+    if name in ("BC", "DeviceBC", "plan_bc_batches"):
+        from . import bc
+        return getattr(bc, name)
     if name == "sample_points":
         from .sampler import sample_points
         return sample_points

@@ -153,6 +153,10 @@ SIGNATURES = {
     "amx_dfit_step": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_int, c_int, c_int, c_int,
                               c_int, vp, vp, vp, c_ll, c_int, vp, c_ll, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                               vp, vp]),
+    "amx_bcfit_work": (c_ll, [c_int, c_int]),
+    "amx_bcfit_steps": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, c_int, vp, vp, vp, vp, c_dbl, c_dbl, c_dbl, c_dbl,
+                                c_dbl, c_int, vp, vp]),
+    "amx_bcfit_eval": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, c_int, vp, vp, vp]),
     "amx_philox":(c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
     "amx_mt_seed": (c_int, [vp, c_int, vp, vp, c_int]),
     "amx_mt_policy_noise": (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_ll, c_ll]),
@@ -167,6 +171,7 @@ AMX_IN_F64, AMX_IN_F32 = 0, 1
 AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
 AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1
 AMX_DFIT_SGD, AMX_DFIT_ADAM = 0, 1
+AMX_BC_MSE, AMX_BC_MLE = 0, 1
 
 
 class AmxNativeError(RuntimeError):

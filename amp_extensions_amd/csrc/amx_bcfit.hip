@@ -1,0 +1,757 @@
+// The behaviour-cloning warm start on the device: BC.fit's training loop
+// (mjrl/mjrl/algos/behavior_cloning.py:106-139) for the policy's S -> 32 -> 32 -> A tanh MLP
+// (mjrl/mjrl/policies/gaussian_mlp.py:7-62), with the MSE loss (behavior_cloning.py:94-104) or
+// the negative mean log-likelihood (behavior_cloning.py:82-92, gaussian_mlp.py:106-122) and
+// torch.optim.Adam.
+//
+// k_bcfit_steps runs n_steps dependent Adam steps in ONE launch of ONE workgroup of 16 waves.
+// The whole policy (8 616 floats at S/A = 197/36) stays in LDS for the launch, in padded
+// row-major images (W1 [32][XS], W2 [32][36], W3 [A16][36], b1, b2, b3, log_std); every
+// parameter has one owner thread, which computes that parameter's gradient, keeps its two Adam
+// moments in registers for the whole launch and applies the update in LDS.  Nothing goes to
+// global memory between steps but the step's loss; theta, the moments and the step count are
+// written back once, at the end.  __syncthreads-style workgroup barriers are the only
+// synchronisation (there is no other workgroup).
+//
+// Every product is a 16x16 tile on the f32 matrix pipe (v_mfma_f32_16x16x4_f32, an exact fp32
+// fma chain in a fixed order, so a fit is bit-reproducible):
+//   P1  layer 1, K = S split in two halves: 8 tiles x 2 halves on the 16 waves -> partials
+//   P1b H1 = tanh(part0 + part1 + b1)                                  (all threads)
+//   P2  H2 = tanh(H1 W2^T + b2)           waves 0-7; wave 8 forms the step's Adam constants
+//       (1 - beta^t in double), wave 9 the column scales of d mu
+//   P3  mu = H2 W3^T + b3; Z = mu - a (MSE) or (a - mu) / sigma (MLE), over the actions in LDS
+//   P4  D2 = ((Z sc) W3) (1 - H2^2)       waves 0-7;  gW3 = (Z^T H2) sc   waves 8-15 (kept in
+//       registers); b3, the log_std gradient (MLE) and the loss on waves 13-15
+//   P5  d1 = (D2 W2) (1 - H1^2)           waves 0-7 (registers);  Adam on W3, gW2 = D2^T H1 on
+//       waves 8-11, b2 on wave 12, log_std on wave 14
+//   P5b D1 = d1 over H1's buffer; Adam on W2
+//   P6  gW1 = D1^T X: 2 ceil(S / 16) tiles, two per wave, each straight into Adam on W1; b1
+//   P7  the next batch (gathered into registers since the top of the step) -> LDS
+// d mu = Z sc with sc = 2 / (64 A) (MSE) or -1 / (64 sigma_c) (MLE).  The owner of a weight is
+// the lane that holds it in the MFMA accumulator of its gradient tile: lane (i = lane & 15,
+// kq = lane >> 4) of the tile's wave owns rows 4 kq .. 4 kq + 3, column i of the tile.
+//
+// The batch indices of all steps are known up front: the rows of step k + 1 are gathered into
+// registers at the top of step k (16 + 4 floats per thread) and stored to LDS at its end, and
+// the indices of step k + 2 are staged the same way, so no step waits on a dependent load.
+// The barriers between phases wait on LDS only (lgkmcnt), never on those loads.
+//
+// k_bcfit_eval is the same forward over all N rows (BC.fit's loss_before / loss_after), 64 rows
+// at a time on as many workgroups as fill the chip: fp32 per row as the reference, fp64 per
+// workgroup, and k_bcfit_eval_sum adds the workgroups' partials in workgroup order.
+#include <math.h>
+
+#include "amx_common.h"
+
+namespace {
+
+constexpr int NH = 32;      // hidden width (both layers)
+constexpr int BB = 64;      // mini-batch rows (BC's batch_size)
+constexpr int NT = 1024;    // threads: 16 waves, 4 per SIMD
+constexpr int NW = NT / 64;
+constexpr int MAXS = 256, MAXA = 64;  // DeviceNPG's limits
+constexpr int HS = 36;      // row stride of the 32-wide images (= 4 mod 32: float4 reads of 8 rows hit 32 banks)
+constexpr int XU = 16, AU = 4;        // gathered floats per thread: 64 x 256 / 1024, 64 x 64 / 1024
+constexpr int EVAL_MAXB = 1024;       // most workgroups of k_bcfit_eval
+constexpr int LOSS_MSE = 0, LOSS_MLE = 1;
+
+typedef float pf4 __attribute__((ext_vector_type(4)));
+
+// LDS image in floats.  The parameters come first ([0, X)); pads are zero for the whole launch.
+struct Lay {
+  int S, A, KP, XS, A16, AS, CT, KT;
+  int W1, W2, W3, b1, b2, b3, ls, X, ACT, H1, H2, D2, PART, SC, ADAM, IDX, total;
+  __host__ __device__ Lay(int S_, int A_) : S(S_), A(A_) {
+    KP = (S + 15) / 16 * 16;
+    XS = KP + 4 + (KP % 32 ? 16 : 0);  // = 4 mod 32
+    A16 = (A + 15) / 16 * 16;
+    AS = A16 + 4;
+    CT = A16 / 16;
+    KT = KP / 16;
+    int o = 0;
+    W1 = o; o += NH * XS;
+    W2 = o; o += NH * HS;
+    W3 = o; o += A16 * HS;
+    b1 = o; o += NH;
+    b2 = o; o += NH;
+    b3 = o; o += MAXA;
+    ls = o; o += MAXA;
+    X = o; o += BB * XS;        // the batch's observations | zeros
+    ACT = o; o += BB * AS;      // the batch's actions, then Z in place
+    H1 = o; o += BB * HS;       // tanh activations; D1 from P5b on
+    H2 = o; o += BB * HS;
+    D2 = o; o += BB * HS;
+    PART = H2;                  // layer 1's two K-half partials [2][64][HS]: H2 and D2 are idle then
+    SC = o; o += MAXA;          // column scales of d mu
+    ADAM = o; o += 8;
+    IDX = o; o += 2 * BB;       // row indices of the next two steps (int)
+    total = o;
+  }
+  __host__ __device__ size_t bytes() const { return (size_t)total * sizeof(float); }
+};
+
+// offsets of the reference's flat parameter order: W1 | b1 | W2 | b2 | W3 | b3 | log_std
+struct Flat {
+  int b1, W2, b2, W3, b3, ls, P;
+  __host__ __device__ Flat(int S, int A) {
+    b1 = NH * S;
+    W2 = b1 + NH;
+    b2 = W2 + NH * NH;
+    W3 = b2 + NH;
+    b3 = W3 + A * NH;
+    ls = b3 + A;
+    P = ls + A;
+  }
+};
+
+struct Adam {
+  float step, bc2s, omb1, b2, omb2, eps, wd;
+};
+
+// amx_vfit.hip's adam_consts / adam_math: the bias corrections bc = 1 - beta^t formed in double;
+// torch.optim.Adam's single-tensor update op for op: grad.add(p, alpha=wd); exp_avg.lerp_;
+// exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2); denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_.
+__device__ inline Adam adam_consts(double bc1, double bc2, double lr, double b1, double b2, double eps, double wd) {
+  Adam a;
+  a.step = (float)(lr / bc1);
+  a.bc2s = (float)sqrt(bc2);
+  a.omb1 = (float)(1.0 - b1);
+  a.b2 = (float)b2;
+  a.omb2 = (float)(1.0 - b2);
+  a.eps = (float)eps;
+  a.wd = (float)wd;
+  return a;
+}
+
+__device__ inline void adam_lds(float* w, float& m, float& v, float g, const Adam& a) {
+  float p = *w;
+  g = g + a.wd * p;
+  m = m + (g - m) * a.omb1;
+  v = v * a.b2 + (a.omb2 * g) * g;
+  const float den = sqrtf(v) / a.bc2s + a.eps;
+  *w = p - a.step * (m / den);
+}
+
+// workgroup barrier that waits on LDS traffic only: the gathered rows of the next step stay in
+// flight across it (amx_npg.hip's lds_barrier)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__device__ __forceinline__ pf4 mma(float a, float b, pf4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+__device__ inline float wave_sum_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ inline double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// row r of MFMA step s (0..15) for lane group kq of a K = 64-rows product: the two groups of a
+// 32-lane half read rows 4 apart (16 banks apart at a row stride = 4 mod 32)
+__device__ __forceinline__ int krow(int s, int kq) { return 16 * (s >> 2) + 4 * kq + (s & 3); }
+
+// C tile += A[16 rows i][K] B[16 rows i][K]^T, both row-major in LDS with K contiguous
+// (float4 per lane and 16 k: lane group kq takes k = 16 jj + 4 kq .. + 3)
+__device__ __forceinline__ pf4 tile_nt(const float* __restrict__ a, const float* __restrict__ b, int jj0, int jj1,
+                                       pf4 acc) {
+  for (int jj = jj0; jj < jj1; ++jj) {
+    const pf4 x = *reinterpret_cast<const pf4*>(a + 16 * jj);
+    const pf4 w = *reinterpret_cast<const pf4*>(b + 16 * jj);
+    acc = mma(x.x, w.x, acc);
+    acc = mma(x.y, w.y, acc);
+    acc = mma(x.z, w.z, acc);
+    acc = mma(x.w, w.w, acc);
+  }
+  return acc;
+}
+
+// C tile = sum over the 64 rows r of A[r][ca] B[r][cb] (A: stride lda, B: stride ldb; ca / cb
+// already include the lane's column)
+__device__ __forceinline__ pf4 tile_tn(const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb,
+                                       int kq) {
+  pf4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int s = 0; s < 16; ++s) {
+    const int r = krow(s, kq);
+    acc = mma(a[r * lda], b[r * ldb], acc);
+  }
+  return acc;
+}
+
+// The thread's indices, re-derived at every phase of a step from a thread id the compiler cannot
+// see through: otherwise it hoists every per-thread LDS address of the step out of the step
+// loop, which costs some 80 registers (spilled to scratch at 128 per thread) for a few integer
+// operations saved.
+struct Tid {
+  int t, lane, wave, i, kq;
+  __device__ __forceinline__ Tid() {
+    t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    lane = t & 63;
+    wave = t >> 6;
+    i = lane & 15;
+    kq = lane >> 4;
+  }
+};
+
+// a phase's own copies of the kernel's thread indices (shadowing them)
+#define BCFIT_PHASE_TID()                                                                        \
+  const Tid q_;                                                                                  \
+  const int t = q_.t, lane = q_.lane, wave = q_.wave, i = q_.i, kq = q_.kq, ct3 = (wave - 8) >> 1, \
+            jt3 = wave & 1;                                                                      \
+  (void)t; (void)lane; (void)i; (void)kq; (void)ct3; (void)jt3
+
+// sum over n (a multiple of 8) elements p[e * ld] of f(element), in element order.  The reads
+// go out 8 at a time: written as a plain loop, every read waits for the add before it (some
+// 100 clocks each, three such sums per step on the critical path).
+template <typename F>
+__device__ __forceinline__ float strided_sum(const float* __restrict__ p, int ld, int n, F f) {
+  float s = 0.f;
+#pragma unroll 1
+  for (int e0 = 0; e0 < n; e0 += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = p[(e0 + u) * ld];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += f(v[u]);
+  }
+  return s;
+}
+
+struct StepConsts {
+  long long t;  // Adam's step count of this step (1-based)
+  double lr, beta1, beta2, eps, wd;
+};
+
+// The forward of the 64 rows in X / ACT (P1 - P3): leaves H1, H2 and Z (over ACT).  STEP: the
+// idle waves of P2 form the step's Adam constants and the d mu column scales.
+template <bool STEP>
+__device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, int loss_type, const StepConsts* sc) {
+  {  // P1
+    const Tid q;
+    const int wave = q.wave, i = q.i, kq = q.kq;
+    const int tile = wave & 7, kh = wave >> 3, rt = tile >> 1, jt = tile & 1;
+    const int jj0 = kh ? L.KT / 2 : 0, jj1 = kh ? L.KT : L.KT / 2;
+    pf4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = tile_nt(sm + L.X + (rt * 16 + i) * L.XS + 4 * kq, sm + L.W1 + (jt * 16 + i) * L.XS + 4 * kq, jj0, jj1, acc);
+    float* pp = sm + L.PART + kh * BB * HS + (rt * 16 + 4 * kq) * HS + jt * 16 + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pp[r * HS] = acc[r];
+  }
+  lds_barrier();
+  const Tid q1;
+#pragma unroll
+  for (int e = q1.t; e < BB * NH; e += NT) {  // P1b
+    const int r = e >> 5, j = e & 31;
+    const float z = (sm[L.PART + r * HS + j] + sm[L.PART + BB * HS + r * HS + j]) + sm[L.b1 + j];
+    sm[L.H1 + r * HS + j] = tanhf(z);
+  }
+  lds_barrier();
+  const Tid q2;
+  const int lane = q2.lane, wave = q2.wave, i = q2.i, kq = q2.kq;
+  if (wave < 8) {  // P2
+    const int rt = wave >> 1, jt = wave & 1;
+    pf4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = tile_nt(sm + L.H1 + (rt * 16 + i) * HS + 4 * kq, sm + L.W2 + (jt * 16 + i) * HS + 4 * kq, 0, 2, acc);
+    const float b = sm[L.b2 + jt * 16 + i];
+    float* ph = sm + L.H2 + (rt * 16 + 4 * kq) * HS + jt * 16 + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ph[r * HS] = tanhf(acc[r] + b);
+  } else if (STEP && wave == 8) {
+    // the two powers side by side on lanes 0 and 1
+    const double bc = 1.0 - pow(lane == 1 ? sc->beta2 : sc->beta1, (double)sc->t), bc2 = __shfl(bc, 1);
+    if (lane == 0) *reinterpret_cast<Adam*>(sm + L.ADAM) = adam_consts(bc, bc2, sc->lr, sc->beta1, sc->beta2, sc->eps, sc->wd);
+  } else if (STEP && wave == 9) {
+    float s = 0.f;
+    if (lane < L.A) s = loss_type == LOSS_MLE ? -1.f / ((float)BB * expf(sm[L.ls + lane])) : 2.f / (float)(BB * L.A);
+    sm[L.SC + lane] = s;
+  }
+  lds_barrier();
+  const Tid q3;
+  for (int item = q3.wave; item < 4 * L.CT; item += NW) {  // P3
+    const int i = q3.i, kq = q3.kq;
+    const int rt = item / L.CT, ct = item - rt * L.CT, c = ct * 16 + i;
+    pf4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = tile_nt(sm + L.H2 + (rt * 16 + i) * HS + 4 * kq, sm + L.W3 + c * HS + 4 * kq, 0, 2, acc);
+    const float b = sm[L.b3 + c];
+    const float sig = loss_type == LOSS_MLE ? expf(sm[L.ls + c]) : 1.f;
+    float* pz = sm + L.ACT + (rt * 16 + 4 * kq) * L.AS + c;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float mu = acc[r] + b, a = pz[r * L.AS];
+      pz[r * L.AS] = c < L.A ? (loss_type == LOSS_MLE ? (a - mu) / sig : mu - a) : 0.f;
+    }
+  }
+  lds_barrier();
+}
+
+// row r's term of the loss from Z, fp32 as the reference: sum_c (mu - a)^2 (MSE) or LL_r (MLE)
+__device__ inline float row_term(const float* __restrict__ sm, const Lay& L, int loss_type, int r) {
+  // over the padded width: Z and log_std are zero past A
+  const float s = strided_sum(sm + L.ACT + r * L.AS, 1, L.A16, [](float z) { return z * z; });
+  if (loss_type == LOSS_MSE) return s;
+  const float sl = strided_sum(sm + L.ls, 1, L.A16, [](float x) { return x; });
+  return (-0.5f * s - sl) - (float)(0.5 * (double)L.A * 1.8378770664093453);  // log(2 pi)
+}
+
+// theta (flat) -> the LDS images; everything else in LDS zero
+__device__ inline void stage_theta(float* __restrict__ sm, const Lay& L, const Flat& F, const float* __restrict__ theta) {
+  const int t = threadIdx.x;
+  for (int e = t; e < L.total; e += NT) sm[e] = 0.f;
+  __syncthreads();
+  for (int e = t; e < NH * L.S; e += NT) {
+    const int j = e / L.S, k = e - j * L.S;
+    sm[L.W1 + j * L.XS + k] = theta[e];
+  }
+  for (int e = t; e < NH * NH; e += NT) sm[L.W2 + (e >> 5) * HS + (e & 31)] = theta[F.W2 + e];
+  for (int e = t; e < L.A * NH; e += NT) sm[L.W3 + (e >> 5) * HS + (e & 31)] = theta[F.W3 + e];
+  if (t < NH) {
+    sm[L.b1 + t] = theta[F.b1 + t];
+    sm[L.b2 + t] = theta[F.b2 + t];
+  }
+  if (t < L.A) {
+    sm[L.b3 + t] = theta[F.b3 + t];
+    sm[L.ls + t] = theta[F.ls + t];
+  }
+}
+
+struct StepArgs {
+  int S, A, N, n_steps, loss_type;
+  const float* obs;
+  long long ldo;
+  const float* act;
+  long long lda;
+  const int32_t* idx;
+  float* theta;
+  float* am;
+  float* av;
+  long long* adam_step;
+  double lr, beta1, beta2, eps, wd;
+  float* step_loss;
+};
+
+__global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const Lay L(a.S, a.A);
+  const Flat F(a.S, a.A);
+  const int S = a.S, A = a.A;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i = lane & 15, kq = lane >> 4;
+  const bool mle = a.loss_type == LOSS_MLE;
+  int* sidx = reinterpret_cast<int*>(sm + L.IDX);
+
+  stage_theta(sm, L, F, a.theta);
+
+  // ---- ownership: flat offset of each owned parameter (-1: none) and its moments ---------------
+  // W1: tiles T = wave + 16 u (jt = T & 1, kt = T >> 1); W3: waves 8-15 (ct = (wave - 8) >> 1,
+  // jt = wave & 1); W2: waves 8-11 (j2t = (wave - 8) >> 1, j1t = wave & 1); b2 / b3 / log_std /
+  // b1: lanes of waves 12 / 13 / 14 / 15
+  float m1[2][4], v1[2][4], m3[4], v3[4], m2[4], v2[4], ms = 0.f, vs = 0.f;
+  int os = -1;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int T = wave + NW * u, jt = T & 1, k = (T >> 1) * 16 + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const bool own = T < 2 * L.KT && k < S;
+      const int o = (jt * 16 + 4 * kq + r) * S + k;
+      m1[u][r] = own ? a.am[o] : 0.f;
+      v1[u][r] = own ? a.av[o] : 0.f;
+    }
+  }
+  const int ct3 = (wave - 8) >> 1, jt3 = wave & 1;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = ct3 * 16 + 4 * kq + r;
+    const bool own3 = wave >= 8 && ct3 < L.CT && c < A;
+    const int o3 = F.W3 + c * NH + jt3 * 16 + i;
+    m3[r] = own3 ? a.am[o3] : 0.f;
+    v3[r] = own3 ? a.av[o3] : 0.f;
+    const bool own2 = wave >= 8 && wave < 12;
+    const int o2 = F.W2 + (ct3 * 16 + 4 * kq + r) * NH + jt3 * 16 + i;
+    m2[r] = own2 ? a.am[o2] : 0.f;
+    v2[r] = own2 ? a.av[o2] : 0.f;
+  }
+  if (wave == 12 && lane < NH) os = F.b2 + lane;
+  if (wave == 13 && lane < A) os = F.b3 + lane;
+  if (wave == 14 && lane < A && mle) os = F.ls + lane;
+  if (wave == 15 && lane < NH) os = F.b1 + lane;
+  if (os >= 0) {
+    ms = a.am[os];
+    vs = a.av[os];
+  }
+  const long long t0 = a.adam_step[0];
+
+  // ---- the first batch, and the indices of the first two ----------------------------------------
+  auto clampi = [&](int v) { return v < 0 ? 0 : (v >= a.N ? a.N - 1 : v); };
+  if (t < BB) {
+    sidx[t] = clampi(a.idx[t]);
+    if (a.n_steps > 1) sidx[BB + t] = clampi(a.idx[BB + t]);
+  }
+  __syncthreads();
+  float xr[XU], ar[AU];
+  // gather map: wave w takes rows 4 w .. 4 w + 3; lane = column within a 64-column group
+  auto gather = [&](const int* rows, int lane, int wave) {
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int c = lane + 64 * (u & 3);
+      xr[u] = c < S ? a.obs[(long long)rows[wave * 4 + (u >> 2)] * a.ldo + c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u) ar[u] = lane < A ? a.act[(long long)rows[wave * 4 + u] * a.lda + lane] : 0.f;
+  };
+  auto scatter = [&](int lane, int wave) {
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int c = lane + 64 * (u & 3);
+      if (c < S) sm[L.X + (wave * 4 + (u >> 2)) * L.XS + c] = xr[u];
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u)
+      if (lane < A) sm[L.ACT + (wave * 4 + u) * L.AS + lane] = ar[u];
+  };
+  gather(sidx, lane, wave);
+  scatter(lane, wave);
+  __syncthreads();
+
+  for (int k = 0; k < a.n_steps; ++k) {
+    // the next step's rows and the step after's indices: in flight until P7
+    int inext = 0;
+    {
+      BCFIT_PHASE_TID();
+      if (k + 1 < a.n_steps) gather(sidx + ((k + 1) & 1) * BB, lane, wave);
+      if (k + 2 < a.n_steps && t < BB) inext = a.idx[(long long)(k + 2) * BB + t];
+    }
+
+    StepConsts sc = {t0 + k + 1, a.lr, a.beta1, a.beta2, a.eps, a.wd};
+    forward<true>(sm, L, a.loss_type, &sc);
+    const Adam ad = *reinterpret_cast<const Adam*>(sm + L.ADAM);
+
+    // ---- P4 -------------------------------------------------------------------------------------
+    pf4 g3 = {0.f, 0.f, 0.f, 0.f};
+    float gls = 0.f;
+    {
+    BCFIT_PHASE_TID();
+    if (wave < 8) {
+      // D2 = ((Z sc) W3) (1 - H2^2): rows rt, hidden units jt
+      const int rt = wave >> 1, jt = wave & 1;
+      pf4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* pz = sm + L.ACT + (rt * 16 + i) * L.AS + 4 * kq;
+      const float* ps = sm + L.SC + 4 * kq;
+      const float* pw = sm + L.W3 + (4 * kq) * HS + jt * 16 + i;
+      for (int jj = 0; jj < L.CT; ++jj) {
+        const pf4 z = *reinterpret_cast<const pf4*>(pz + 16 * jj) * *reinterpret_cast<const pf4*>(ps + 16 * jj);
+        const float* w = pw + 16 * jj * HS;
+        acc = mma(z.x, w[0], acc);
+        acc = mma(z.y, w[HS], acc);
+        acc = mma(z.z, w[2 * HS], acc);
+        acc = mma(z.w, w[3 * HS], acc);
+      }
+      const float* ph = sm + L.H2 + (rt * 16 + 4 * kq) * HS + jt * 16 + i;
+      float* pd = sm + L.D2 + (rt * 16 + 4 * kq) * HS + jt * 16 + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float h = ph[r * HS];
+        pd[r * HS] = acc[r] * (1.f - h * h);
+      }
+    } else {
+      if (ct3 < L.CT) {  // gW3[c][j] = sc[c] sum_r Z[r][c] H2[r][j]
+        g3 = tile_tn(sm + L.ACT + ct3 * 16 + i, L.AS, sm + L.H2 + jt3 * 16 + i, HS, kq);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) g3[r] *= sm[L.SC + ct3 * 16 + 4 * kq + r];
+      }
+      if (wave == 13 && lane < A) {  // b3
+        const float s = strided_sum(sm + L.ACT + lane, L.AS, BB, [](float x) { return x; });
+        adam_lds(sm + L.b3 + lane, ms, vs, s * sm[L.SC + lane], ad);
+      } else if (wave == 14 && lane < A && mle) {  // d log_std_c = -(1 / 64) sum_r (z^2 - 1)
+        const float s = strided_sum(sm + L.ACT + lane, L.AS, BB, [](float z) { return z * z - 1.f; });
+        gls = -s * (1.f / BB);  // applied in P5: the loss (wave 15) reads log_std in this phase
+      } else if (wave == 15) {  // the step's loss
+        const float tot = wave_sum_f(row_term(sm, L, a.loss_type, lane));
+        if (lane == 0) a.step_loss[k] = mle ? -tot * (1.f / BB) : tot / (float)(BB * A);
+      }
+    }
+    }
+    lds_barrier();
+
+    // ---- P5 -------------------------------------------------------------------------------------
+    float d1[4] = {0.f, 0.f, 0.f, 0.f};
+    pf4 g2 = {0.f, 0.f, 0.f, 0.f};
+    {
+    BCFIT_PHASE_TID();
+    if (wave < 8) {
+      // d1 = (D2 W2) (1 - H1^2)
+      const int rt = wave >> 1, jt = wave & 1;
+      pf4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* pz = sm + L.D2 + (rt * 16 + i) * HS + 4 * kq;
+      const float* pw = sm + L.W2 + (4 * kq) * HS + jt * 16 + i;
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const pf4 z = *reinterpret_cast<const pf4*>(pz + 16 * jj);
+        const float* w = pw + 16 * jj * HS;
+        acc = mma(z.x, w[0], acc);
+        acc = mma(z.y, w[HS], acc);
+        acc = mma(z.z, w[2 * HS], acc);
+        acc = mma(z.w, w[3 * HS], acc);
+      }
+      const float* ph = sm + L.H1 + (rt * 16 + 4 * kq) * HS + jt * 16 + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float h = ph[r * HS];
+        d1[r] = acc[r] * (1.f - h * h);
+      }
+    } else {
+      if (ct3 < L.CT) {  // Adam on W3 (P4 was its last reader)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = ct3 * 16 + 4 * kq + r;
+          if (c < A) adam_lds(sm + L.W3 + c * HS + jt3 * 16 + i, m3[r], v3[r], g3[r], ad);
+        }
+      }
+      if (wave < 12) {  // gW2[j2][j1] = sum_r D2[r][j2] H1[r][j1]
+        g2 = tile_tn(sm + L.D2 + ct3 * 16 + i, HS, sm + L.H1 + jt3 * 16 + i, HS, kq);
+      } else if (wave == 12 && lane < NH) {  // b2
+        const float s = strided_sum(sm + L.D2 + lane, HS, BB, [](float x) { return x; });
+        adam_lds(sm + L.b2 + lane, ms, vs, s, ad);
+      } else if (wave == 14 && lane < A && mle) {
+        adam_lds(sm + L.ls + lane, ms, vs, gls, ad);
+      }
+    }
+    }
+    lds_barrier();
+
+    // ---- P5b: D1 over H1 (its readers are done); Adam on W2 (P5 was its last reader) -----------
+    {
+    BCFIT_PHASE_TID();
+    if (wave < 8) {
+      float* pd = sm + L.H1 + ((wave >> 1) * 16 + 4 * kq) * HS + (wave & 1) * 16 + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pd[r * HS] = d1[r];
+    } else if (wave < 12) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        adam_lds(sm + L.W2 + (ct3 * 16 + 4 * kq + r) * HS + jt3 * 16 + i, m2[r], v2[r], g2[r], ad);
+    }
+    }
+    lds_barrier();
+
+    // ---- P6: gW1[j][k] = sum_r D1[r][j] X[r][k], straight into Adam -----------------------------
+    {
+    BCFIT_PHASE_TID();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int T = wave + NW * u, jt = T & 1, kc = (T >> 1) * 16 + i;
+      if (T < 2 * L.KT) {
+        const pf4 g = tile_tn(sm + L.H1 + jt * 16 + i, HS, sm + L.X + kc, L.XS, kq);
+        if (kc < S) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) adam_lds(sm + L.W1 + (jt * 16 + 4 * kq + r) * L.XS + kc, m1[u][r], v1[u][r], g[r], ad);
+        }
+      }
+    }
+    if (wave == 15 && lane < NH) {  // b1
+      const float s = strided_sum(sm + L.H1 + lane, HS, BB, [](float x) { return x; });
+      adam_lds(sm + L.b1 + lane, ms, vs, s, ad);
+    }
+    }
+    lds_barrier();
+
+    // ---- P7: the next batch -----------------------------------------------------------------------
+    {
+      BCFIT_PHASE_TID();
+      if (k + 1 < a.n_steps) scatter(lane, wave);
+      if (k + 2 < a.n_steps && t < BB) sidx[(k & 1) * BB + t] = clampi(inext);
+    }
+    lds_barrier();
+  }
+
+  // ---- write-back -------------------------------------------------------------------------------
+  __syncthreads();
+  for (int e = t; e < NH * S; e += NT) {
+    const int j = e / S, k = e - j * S;
+    a.theta[e] = sm[L.W1 + j * L.XS + k];
+  }
+  for (int e = t; e < NH * NH; e += NT) a.theta[F.W2 + e] = sm[L.W2 + (e >> 5) * HS + (e & 31)];
+  for (int e = t; e < A * NH; e += NT) a.theta[F.W3 + e] = sm[L.W3 + (e >> 5) * HS + (e & 31)];
+  if (t < NH) {
+    a.theta[F.b1 + t] = sm[L.b1 + t];
+    a.theta[F.b2 + t] = sm[L.b2 + t];
+  }
+  if (t < A) {
+    a.theta[F.b3 + t] = sm[L.b3 + t];
+    if (mle) a.theta[F.ls + t] = sm[L.ls + t];  // MSE: log_std has no gradient, no moment, no step
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int T = wave + NW * u, jt = T & 1, kc = (T >> 1) * 16 + i;
+    if (T < 2 * L.KT && kc < S) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = (jt * 16 + 4 * kq + r) * S + kc;
+        a.am[o] = m1[u][r];
+        a.av[o] = v1[u][r];
+      }
+    }
+  }
+  if (wave >= 8) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int c = ct3 * 16 + 4 * kq + r;
+      if (ct3 < L.CT && c < A) {
+        const int o3 = F.W3 + c * NH + jt3 * 16 + i;
+        a.am[o3] = m3[r];
+        a.av[o3] = v3[r];
+      }
+      if (wave < 12) {
+        const int o2 = F.W2 + c * NH + jt3 * 16 + i;
+        a.am[o2] = m2[r];
+        a.av[o2] = v2[r];
+      }
+    }
+  }
+  if (os >= 0) {
+    a.am[os] = ms;
+    a.av[os] = vs;
+  }
+  if (t == 0) a.adam_step[0] = t0 + a.n_steps;
+}
+
+struct EvalArgs {
+  int S, A, N, loss_type;
+  const float* obs;
+  long long ldo;
+  const float* act;
+  long long lda;
+  const float* theta;
+  double* partials;
+};
+
+__global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const Lay L(a.S, a.A);
+  const Flat F(a.S, a.A);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  stage_theta(sm, L, F, a.theta);
+  __syncthreads();
+  double bsum = 0.0;
+  const int chunks = (a.N + BB - 1) / BB;
+  for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+    const int r0 = ch * BB;
+    // rows past N read row N - 1 and are left out of the sum
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int c = lane + 64 * (u & 3), r = wave * 4 + (u >> 2);
+      const int g = r0 + r < a.N ? r0 + r : a.N - 1;
+      if (c < a.S) sm[L.X + r * L.XS + c] = a.obs[(long long)g * a.ldo + c];
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int r = wave * 4 + u;
+      const int g = r0 + r < a.N ? r0 + r : a.N - 1;
+      if (lane < a.A) sm[L.ACT + r * L.AS + lane] = a.act[(long long)g * a.lda + lane];
+    }
+    __syncthreads();
+    forward<false>(sm, L, a.loss_type, nullptr);
+    if (wave == 0) {
+      const double v = r0 + lane < a.N ? (double)row_term(sm, L, a.loss_type, lane) : 0.0;
+      bsum += wave_sum_d(v);
+    }
+    __syncthreads();
+  }
+  if (t == 0) a.partials[blockIdx.x] = bsum;
+}
+
+// the workgroups' partials in workgroup order -> mean((mu - a)^2) or -mean(LL)
+__global__ void k_bcfit_eval_sum(const double* __restrict__ partials, int nb, int N, int A, int loss_type,
+                                 double* __restrict__ out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += partials[b];
+    out[0] = loss_type == LOSS_MLE ? -s / (double)N : s / ((double)N * (double)A);
+  }
+}
+
+int check_shape(const char* fn, int S, int A) {
+  AMX_CHECK_ARG(S > 0 && S <= MAXS && A > 0 && A <= MAXA, "%s: S=%d (1..%d), A=%d (1..%d)", fn, S, MAXS, A, MAXA);
+  return AMX_OK;
+}
+
+int check_data(const char* fn, const amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act,
+               long long lda, int loss_type) {
+  int rc = check_shape(fn, ctx->S, ctx->A);
+  if (rc) return rc;
+  AMX_CHECK_ARG(N > 0, "%s: N=%d", fn, N);
+  AMX_CHECK_ARG(obs && act, "%s: null obs / act", fn);
+  AMX_CHECK_ARG(ldo >= ctx->S && lda >= ctx->A, "%s: ldo=%lld < S=%d or lda=%lld < A=%d", fn, ldo, ctx->S, lda, ctx->A);
+  AMX_CHECK_ARG(loss_type == LOSS_MSE || loss_type == LOSS_MLE, "%s: loss_type=%d (0 = MSE, 1 = MLE)", fn, loss_type);
+  return AMX_OK;
+}
+
+template <typename K>
+int allow_lds(K kern, size_t bytes) {
+  AMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)bytes));
+  return AMX_OK;
+}
+
+}  // namespace
+
+extern "C" long long amx_bcfit_work(int S, int A) {
+  if (check_shape("amx_bcfit_work", S, A)) return -1;
+  return (long long)EVAL_MAXB * (long long)sizeof(double);
+}
+
+extern "C" int amx_bcfit_steps(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+                               const int32_t* idx, int n_steps, float* theta, float* adam_m, float* adam_v,
+                               long long* adam_step, double lr, double beta1, double beta2, double eps,
+                               double weight_decay, int loss_type, float* step_loss, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_bcfit_steps: null ctx");
+  AMX_CHECK_ARG(n_steps >= 0, "amx_bcfit_steps: n_steps=%d", n_steps);
+  AMX_CHECK_ARG(idx, "amx_bcfit_steps: null idx");
+  int rc = check_data("amx_bcfit_steps", ctx, N, obs, ldo, act, lda, loss_type);
+  if (rc) return rc;
+  AMX_CHECK_ARG(theta && adam_m && adam_v && adam_step && step_loss,
+                "amx_bcfit_steps: null theta / adam_m / adam_v / adam_step / step_loss");
+  AMX_CHECK_ARG(((uintptr_t)adam_step & 7u) == 0, "amx_bcfit_steps: misaligned adam_step");
+  AMX_CHECK_ARG(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 &&
+                    weight_decay >= 0.0,
+                "amx_bcfit_steps: lr=%g betas=(%g, %g) eps=%g weight_decay=%g", lr, beta1, beta2, eps, weight_decay);
+  if (n_steps == 0) return AMX_OK;
+  const Lay L(ctx->S, ctx->A);
+  AMX_CHECK_ARG(L.bytes() <= 160 * 1024, "amx_bcfit_steps: %zu B of LDS", L.bytes());
+  rc = allow_lds(k_bcfit_steps, L.bytes());
+  if (rc) return rc;
+  StepArgs a = {ctx->S, ctx->A, N, n_steps, loss_type, obs, ldo, act, lda, idx, theta, adam_m, adam_v, adam_step,
+                lr, beta1, beta2, eps, weight_decay, step_loss};
+  hipLaunchKernelGGL(k_bcfit_steps, dim3(1), dim3(NT), L.bytes(), (hipStream_t)stream, a);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+extern "C" int amx_bcfit_eval(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+                              const float* theta, int loss_type, void* work, double* loss, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_bcfit_eval: null ctx");
+  int rc = check_data("amx_bcfit_eval", ctx, N, obs, ldo, act, lda, loss_type);
+  if (rc) return rc;
+  AMX_CHECK_ARG(theta && work && loss, "amx_bcfit_eval: null theta / work / loss");
+  AMX_CHECK_ARG(((uintptr_t)work & 7u) == 0 && ((uintptr_t)loss & 7u) == 0, "amx_bcfit_eval: misaligned work / loss");
+  const Lay L(ctx->S, ctx->A);
+  AMX_CHECK_ARG(L.bytes() <= 160 * 1024, "amx_bcfit_eval: %zu B of LDS", L.bytes());
+  rc = allow_lds(k_bcfit_eval, L.bytes());
+  if (rc) return rc;
+  const int chunks = (N + BB - 1) / BB;
+  int nb = ctx->n_cus > 0 ? ctx->n_cus : 1;  // one workgroup per CU (the image takes most of its LDS)
+  if (nb > chunks) nb = chunks;
+  if (nb > EVAL_MAXB) nb = EVAL_MAXB;
+  EvalArgs a = {ctx->S, ctx->A, N, loss_type, obs, ldo, act, lda, theta, (double*)work};
+  hipLaunchKernelGGL(k_bcfit_eval, dim3(nb), dim3(NT), L.bytes(), (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_bcfit_eval_sum, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)work, nb, N, ctx->A,
+                     loss_type, loss);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}

@@ -800,6 +800,53 @@ int amx_dfit_step(amx_ctx* ctx, int loss_type, int optim, double lr, double p1, 
                   float* state1, float* state2, long long* step, float* work, double* metrics,
                   void* stream);
 
+/* ---- the behaviour-cloning warm start (BC.train) ------------------------------- */
+
+enum { AMX_BC_MSE = 0, AMX_BC_MLE = 1 };
+
+/* The fit supports what amx_npg_pass supports: the context's S -> 32 -> 32 -> A tanh MLP with
+ * S <= 256 and A <= 64, theta in the reference's flat order (W1 | b1 | W2 | b2 | W3 | b3 |
+ * log_std, amx_npg_param_count floats), and mini-batches of 64 rows.
+ * amx_bcfit_work: bytes of amx_bcfit_eval's workspace (one fp64 partial per workgroup, 1024
+ * workgroups at most: 8192); amx_bcfit_steps needs none.  Pure host arithmetic; -1 (and
+ * amx_last_error) for another shape. */
+long long amx_bcfit_work(int S, int A);
+
+/* n_steps consecutive mini-batch steps of BC.fit's training loop
+ * (mjrl/mjrl/algos/behavior_cloning.py:121-129) in one launch of one workgroup: step k gathers
+ * rows idx[64 k .. 64 k + 63] of obs [N, ldo] and act [N, lda] (fp32, device: the reference's
+ * torch.from_numpy(obs[idx]).float() applied to the whole set once), runs the policy's forward
+ * mu = W3 tanh(W2 tanh(W1 x + b1) + b2) + b3 (gaussian_mlp.py:117 through FCNetwork with
+ * identity transformations), the loss
+ *   AMX_BC_MSE  mean over the 64 A elements of (mu - a)^2            (behavior_cloning.py:94-104),
+ *   AMX_BC_MLE  -mean over the 64 rows of LL, LL = -0.5 sum z^2 - sum log_std - 0.5 A log(2 pi),
+ *               z = (a - mu) / exp(log_std)   (behavior_cloning.py:82-92, gaussian_mlp.py:117-121),
+ * autograd's backward and torch.optim.Adam's single-tensor update (no amsgrad; weight_decay
+ * added to every gradient) exactly as amx_vfit_epoch states it, t = adam_step[0] + k + 1 with
+ * beta^t formed in double.  Under AMX_BC_MSE log_std has no gradient: it, and its entries of
+ * adam_m / adam_v, are left untouched (torch's Adam skips parameters whose grad is None).
+ * log_std is not clamped.  step_loss[k] (device, n_steps floats) = step k's fp32 loss.
+ * theta, adam_m, adam_v (amx_npg_param_count floats each; moments zero before the first step)
+ * and adam_step[0] (+= n_steps) are read at the start of the launch and written at its end;
+ * in between the parameters live in LDS and each parameter's moments in registers of the
+ * thread that owns it.  All arithmetic is fp32 on the f32 matrix pipe in a fixed order, so
+ * cutting a run of steps into several calls changes no bit of the result.  idx entries must
+ * lie in [0, N) (the kernel clamps).  n_steps = 0 launches nothing.  No workgroup waits on
+ * another: there is only one. */
+int amx_bcfit_steps(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act,
+                    long long lda, const int32_t* idx, int n_steps, float* theta, float* adam_m,
+                    float* adam_v, long long* adam_step, double lr, double beta1, double beta2,
+                    double eps, double weight_decay, int loss_type, float* step_loss,
+                    void* stream);
+
+/* The loss of theta over all N rows, BC.fit's loss_before / loss_after
+ * (behavior_cloning.py:115-117, 137-138): the same forward, 64 rows at a time on one workgroup
+ * per compute unit; per-row terms in fp32, summed in fp64 per workgroup and then in workgroup
+ * order into loss[0] (device).  work: amx_bcfit_work bytes.  Two launches on `stream`. */
+int amx_bcfit_eval(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act,
+                   long long lda, const float* theta, int loss_type, void* work, double* loss,
+                   void* stream);
+
 /* ---- RNG ----------------------------------------------------------------------- */
 
 /* Philox4x32-10 block for (key = seed, counter = {ctr0, ctr1, ctr2, ctr3}), written
