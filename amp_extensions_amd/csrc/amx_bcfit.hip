@@ -34,16 +34,20 @@
 // The batch indices of all steps are known up front: the rows of step k + 1 are gathered into
 // registers at the top of step k (16 + 4 floats per thread) and stored to LDS at its end, and
 // the indices of step k + 2 are staged the same way, so no step waits on a dependent load.
-// The barriers between phases wait on LDS only (lgkmcnt), never on those loads.
+// The barriers between phases wait on LDS only (amx_common.h's lds_barrier), never on those
+// loads.  Adam's constants and update are amx_optim.h's (AdamConst, adam_apply); the decay is
+// added here.
 //
 // k_bcfit_eval is the same forward over all N rows (BC.fit's loss_before / loss_after), 64 rows
 // at a time on as many workgroups as fill the chip: fp32 per row as the reference, fp64 per
 // workgroup, and k_bcfit_eval_sum adds the workgroups' partials in workgroup order.
 #include <math.h>
 
-#include "amx_common.h"
+#include "amx_optim.h"
 
 namespace {
+
+using amx::lds_barrier;
 
 constexpr int NH = 32;      // hidden width (both layers)
 constexpr int BB = 64;      // mini-batch rows (BC's batch_size)
@@ -105,51 +109,21 @@ struct Flat {
 };
 
 struct Adam {
-  float step, bc2s, omb1, b2, omb2, eps, wd;
+  amx::AdamConst c;
+  float wd;
 };
 
-// amx_vfit.hip's adam_consts / adam_math: the bias corrections bc = 1 - beta^t formed in double;
-// torch.optim.Adam's single-tensor update op for op: grad.add(p, alpha=wd); exp_avg.lerp_;
-// exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2); denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_.
-__device__ inline Adam adam_consts(double bc1, double bc2, double lr, double b1, double b2, double eps, double wd) {
-  Adam a;
-  a.step = (float)(lr / bc1);
-  a.bc2s = (float)sqrt(bc2);
-  a.omb1 = (float)(1.0 - b1);
-  a.b2 = (float)b2;
-  a.omb2 = (float)(1.0 - b2);
-  a.eps = (float)eps;
-  a.wd = (float)wd;
-  return a;
-}
-
+// torch.optim.Adam with weight decay on a parameter in LDS, its moments in registers:
+// grad.add(p, alpha=wd), then amx_optim.h's update
 __device__ inline void adam_lds(float* w, float& m, float& v, float g, const Adam& a) {
   float p = *w;
   g = g + a.wd * p;
-  m = m + (g - m) * a.omb1;
-  v = v * a.b2 + (a.omb2 * g) * g;
-  const float den = sqrtf(v) / a.bc2s + a.eps;
-  *w = p - a.step * (m / den);
+  amx::adam_apply(p, m, v, g, a.c);
+  *w = p;
 }
-
-// workgroup barrier that waits on LDS traffic only: the gathered rows of the next step stay in
-// flight across it (amx_npg.hip's lds_barrier)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ pf4 mma(float a, float b, pf4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ inline float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // row r of MFMA step s (0..15) for lane group kq of a K = 64-rows product: the two groups of a
@@ -266,7 +240,8 @@ __device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, in
   } else if (STEP && wave == 8) {
     // the two powers side by side on lanes 0 and 1
     const double bc = 1.0 - pow(lane == 1 ? sc->beta2 : sc->beta1, (double)sc->t), bc2 = __shfl(bc, 1);
-    if (lane == 0) *reinterpret_cast<Adam*>(sm + L.ADAM) = adam_consts(bc, bc2, sc->lr, sc->beta1, sc->beta2, sc->eps, sc->wd);
+    if (lane == 0)
+      *reinterpret_cast<Adam*>(sm + L.ADAM) = Adam{amx::AdamConst(bc, bc2, sc->lr, sc->beta1, sc->beta2, sc->eps), (float)sc->wd};
   } else if (STEP && wave == 9) {
     float s = 0.f;
     if (lane < L.A) s = loss_type == LOSS_MLE ? -1.f / ((float)BB * expf(sm[L.ls + lane])) : 2.f / (float)(BB * L.A);
@@ -388,7 +363,7 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
   const long long t0 = a.adam_step[0];
 
   // ---- the first batch, and the indices of the first two ----------------------------------------
-  auto clampi = [&](int v) { return v < 0 ? 0 : (v >= a.N ? a.N - 1 : v); };
+  auto clampi = [&](int v) { return amx::clamp_row(v, a.N); };
   if (t < BB) {
     sidx[t] = clampi(a.idx[t]);
     if (a.n_steps > 1) sidx[BB + t] = clampi(a.idx[BB + t]);
@@ -472,7 +447,7 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
         const float s = strided_sum(sm + L.ACT + lane, L.AS, BB, [](float z) { return z * z - 1.f; });
         gls = -s * (1.f / BB);  // applied in P5: the loss (wave 15) reads log_std in this phase
       } else if (wave == 15) {  // the step's loss
-        const float tot = wave_sum_f(row_term(sm, L, a.loss_type, lane));
+        const float tot = amx::wave_sum(row_term(sm, L, a.loss_type, lane));
         if (lane == 0) a.step_loss[k] = mle ? -tot * (1.f / BB) : tot / (float)(BB * A);
       }
     }
@@ -659,7 +634,7 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) {
     forward<false>(sm, L, a.loss_type, nullptr);
     if (wave == 0) {
       const double v = r0 + lane < a.N ? (double)row_term(sm, L, a.loss_type, lane) : 0.0;
-      bsum += wave_sum_d(v);
+      bsum += amx::wave_sum(v);
     }
     __syncthreads();
   }

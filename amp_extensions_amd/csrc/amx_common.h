@@ -1,4 +1,5 @@
-// Shared internals of libamx_hip: context, error plumbing, Philox RNG.
+// Shared internals of libamx_hip: context, error plumbing, small device helpers (wave and
+// workgroup sums, the gather's row clamp, the LDS barrier), Philox RNG.
 // Written for gfx950 (CDNA4, wave64).  Everything here is device-agnostic C++ plus
 // HIP device helpers; the kernels live in amx_*.hip.
 #pragma once
@@ -80,8 +81,44 @@ void set_error(const char* fmt, ...);
 
 #define AMX_CHECK_LAUNCH() AMX_CHECK_HIP(hipGetLastError())
 
+// a function shared between the library's sources that is no part of its ABI
+#define AMX_INTERNAL __attribute__((visibility("hidden")))
+
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// ---- small device helpers -----------------------------------------------------------------
+// Sum over the 64 lanes of a wave by the xor butterfly, offsets 32 down to 1: every lane ends
+// with the total, and the association is fixed (the same bits for the same lane values).
+template <typename T>
+__device__ inline T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Row index i of a gather, clamped into [0, n) (callers validate their index vectors).
+__host__ __device__ inline int clamp_row(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// Sum of v over the NT threads of a workgroup (a power of two) in a fixed tree: halves folded
+// onto each other through red[NT].  Every thread returns the total; the last barrier is behind
+// every write, and a caller that reuses red puts a barrier of its own after reading the result.
+template <int NT>
+__device__ inline double block_sum(double* red, double v) {
+  static_assert(NT > 0 && (NT & (NT - 1)) == 0, "power-of-two thread count");
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// Workgroup barrier for LDS hand-offs: waits for this wave's LDS traffic only, so global loads
+// already issued stay in flight across it (__syncthreads' fence waits for them too).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11), key = 2x32, counter = 4x32 ------------------
 struct u32x4 { uint32_t x, y, z, w; };

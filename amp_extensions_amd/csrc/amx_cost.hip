@@ -20,7 +20,8 @@ __device__ __forceinline__ double dpp_f64(double v) {
 
 // Sum over the wave's 64 lanes, returned to every lane, on the DPP path (no LDS traffic; the
 // same fixed association as amx_step.hip's): quad xor 1, 2, the 8- and 16-lane mirrors, rows
-// 0 -> 1, 2 -> 3 (row_bcast:15), rows 0+1 -> 2, 3 (row_bcast:31), lane 63 read back.
+// 0 -> 1, 2 -> 3 (row_bcast:15), rows 0+1 -> 2, 3 (row_bcast:31), lane 63 read back.  Another
+// association than amx_common.h's butterfly, so this one stays: the cost sums' bits depend on it.
 __device__ inline double wave_sum(double v) {
   v += dpp_f64<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
   v += dpp_f64<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]
@@ -162,15 +163,10 @@ __global__ __launch_bounds__(256) void k_sum_small(const double* __restrict__ pa
   __shared__ double red[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += partials[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  const double tot = amx::block_sum<256>(red, s);
   if (threadIdx.x == 0) {
-    out[0] = red[0];
-    if (mean_out) mean_out[0] = scale * (float)(red[0] / (double)n_rows);  // fp32 product, as torch
+    out[0] = tot;
+    if (mean_out) mean_out[0] = scale * (float)(tot / (double)n_rows);  // fp32 product, as torch
   }
 }
 
@@ -348,15 +344,10 @@ __global__ __launch_bounds__(256) void k_mmd_relabel(RelabelArgs a) {
   for (int i = t; i < a.ne; i += 256)
     s += __longlong_as_double(__hip_atomic_load((const gu64*)(a.eout + 1 + i), __ATOMIC_RELAXED,
                                                 __HIP_MEMORY_SCOPE_AGENT));
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
+  const double tot = amx::block_sum<256>(red, s);
   if (t == 0) {
-    a.eout[0] = red[0];
-    if (a.emean) a.emean[0] = a.escale * (float)(red[0] / (double)a.ne_rows);  // fp32 product, as torch
+    a.eout[0] = tot;
+    if (a.emean) a.emean[0] = a.escale * (float)(tot / (double)a.ne_rows);  // fp32 product, as torch
     __hip_atomic_store((gu32c*)a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }

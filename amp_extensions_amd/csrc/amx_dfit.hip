@@ -10,205 +10,33 @@
 //   gW0 += a0^T U, q0 = m0 * (U W0^T), gW1 += a1^T q0, gw2 += sum_rows m1 * (q0 W1^T).
 //
 //   k_dfit_gather   expert / agent rows through the two index vectors into X[0 : 2 Bt]
-//   amx_gemm_bias_act_t64 x 2   the forward on the fp32 master weights (f32 MFMA)
+//   amx_gemm_bias_act_t64 x 2   the forward on the fp32 master weights (f32 MFMA, amx_gemm64.hip)
 //   k_dfit_head     out, d out by loss type, Z1's three blocks
-//   k_dfit_reg      partial sums of the logged regularizer sum 1/2 W^2 (no gradient)
-//   k_dfit_gemm<NN> Z0 = (Z1 W1) * (h0 > 0);  g = a0 W0
+//   k_optim_sumsq   partial sums of the logged regularizer sum 1/2 W^2 over W0, W1, w2 (no
+//                   gradient; the padding is zero; amx_optim.hip)
+//   k_gemm64<NN>    Z0 = (Z1 W1) * (h0 > 0);  g = a0 W0               (amx_gemm64.hip)
 //   k_dfit_unit     |g| per expert row, U into X[2 Bt : 3 Bt]
-//   k_dfit_gemm<NT> q0 = (U W0^T) * m0 into H0s[2 Bt :];  P1 = (q0 W1^T) * m1
-//   k_dfit_gemm<TN> gW1 = Z1^T H0s, gb1 = column sums of Z1[: 2 Bt];  gW0 = Z0^T X, gb0
+//   k_gemm64<NT>    q0 = (U W0^T) * m0 into H0s[2 Bt :];  P1 = (q0 W1^T) * m1
+//   k_gemm64<TN>    gW1 = Z1^T H0s, gb1 = column sums of Z1[: 2 Bt];  gW0 = Z0^T X, gb0
 //   k_dfit_gw2      gw2 = dout^T h1 + column sums of P1
 //   k_dfit_prep     the metrics (fp64, fixed tree), gb2, the step count and Adam's corrections
-//   k_dfit_update   torch.optim.SGD (momentum, no Nesterov) / Adam on the six padded tensors
+//   k_optim_update  torch.optim.SGD (momentum, no Nesterov) / Adam on the six padded tensors
+//                   (amx_optim.hip)
 //
 // Stream order is the only synchronisation; every sum runs in a fixed order, so a step is
 // bit-reproducible.  Zero-padded weights see a zero gradient and stay exactly 0 with their state.
 #include <math.h>
 
-#include <type_traits>
-
-#include "amx_common.h"
+#include "amx_gemm64.h"
+#include "amx_optim.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using amx::wave_sum;
 
-// ---- 64 x 64 tile products on v_mfma_f32_32x32x2_f32 -------------------------------------
-// Four waves of one 32 x 32 block each, K-tiles of 32 double-buffered in LDS, one barrier per
-// K-tile (k_efit_fwd64's loop, with the global loads two K-tiles ahead).  An operand whose
-// reduction index is its contiguous one in memory ("row form": A of A B, W of A W^T) is staged as 64 rows of 36 floats and read as
-// float4 along k (k_gemm_nt's conflict-free rows); one whose reduction index is its row index
-// ("k form": B of A B, both operands of A^T B) is staged as 32 rows of 64 floats, the rows of
-// the upper k half rotated by 32 columns, and read as scalars: lanes 0-31 (k) and 32-63
-// (k + 16) then hit disjoint banks.  Either way lane (i, h) supplies k = 16 h + q, q = 0..15,
-// of each K-tile, so every output element runs one fp32 FMA chain in ascending k pairs.
-constexpr int GBK = 32, GLD = GBK + 4, GOP = 64 * GLD, GSTAGE = 2 * GOP;
-
-struct GemmArgs {
-  const float* A; int lda;
-  const float* B; int ldb;
-  float* C; int ldc;
-  const float* mask; int ldm, mask_mod;  // C * (mask[row % mask_mod] > 0); mask_mod 0: row
-  float* colsum; int cs_rows;            // k-form A: colsum[m] = sum_{r < cs_rows} A[r][m]
-  int M, N, K;
-};
-
-// this thread's two float4 of the K-tile at k0; x0 = tile origin, nx = extent of the other index
-template <int KF>
-__device__ inline void op_load(const float* __restrict__ P, int ld, int x0, int nx, int k0, int t, f32x4 (&r)[2]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if (KF) {
-      const int c = x0 + (t & 15) * 4, k = k0 + (t >> 4) + 16 * j;
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      r[j] = c < nx ? *reinterpret_cast<const f32x4*>(P + (long long)k * ld + c) : z;
-    } else {
-      const int row = x0 + (t >> 3) + 32 * j;
-      r[j] = *reinterpret_cast<const f32x4*>(P + (long long)row * ld + k0 + (t & 7) * 4);
-    }
-  }
-}
-
-template <int KF>
-__device__ inline void op_store(float* S, int t, const f32x4 (&r)[2]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if (KF) *reinterpret_cast<f32x4*>(S + ((t >> 4) + 16 * j) * 64 + (((t & 15) * 4) ^ (j << 5))) = r[j];
-    else *reinterpret_cast<f32x4*>(S + ((t >> 3) + 32 * j) * GLD + (t & 7) * 4) = r[j];
-  }
-}
-
-template <int KF>
-__device__ inline void op_frag(const float* S, int w, int li, int lh, float (&f)[16]) {
-  if (KF) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) f[q] = S[(lh * 16 + q) * 64 + ((w * 32 + li) ^ (lh << 5))];
-  } else {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(S + (w * 32 + li) * GLD + lh * 16 + v * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) f[4 * v + e] = x[e];
-    }
-  }
-}
-
-// AK: A is given as [K][M] (C = A^T B); BK: B is given as [K][N] (else as W [N][K], C = A W^T)
-template <int AK, int BK>
-__global__ __launch_bounds__(256, 2) void k_dfit_gemm(GemmArgs a) {
-  __shared__ __align__(16) float smem[2 * GSTAGE];
-  const int tn = blockIdx.x, tm = blockIdx.y;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  // register sets: set p receives tile kt + 2 at the top of iteration kt (p = kt & 1) while set
-  // p ^ 1 holds tile kt + 1, stored to the other LDS stage at the iteration's end: two
-  // iterations of MFMAs cover a global load's latency (a 256-row step gives one workgroup per CU)
-  f32x4 ra[2][2], rb[2][2];
-  f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  const int nk = a.K / GBK;
-  op_load<AK>(a.A, a.lda, tm * 64, a.M, 0, t, ra[0]);
-  op_load<BK>(a.B, a.ldb, tn * 64, a.N, 0, t, rb[0]);
-  op_store<AK>(smem, t, ra[0]);
-  op_store<BK>(smem + GOP, t, rb[0]);
-  const int k1 = (nk > 1 ? 1 : 0) * GBK;
-  op_load<AK>(a.A, a.lda, tm * 64, a.M, k1, t, ra[1]);
-  op_load<BK>(a.B, a.ldb, tn * 64, a.N, k1, t, rb[1]);
-  __syncthreads();
-  // column sums of A (the first column tile's workgroups): wave w sums rows 8 w .. 8 w + 7 of
-  // every K-tile for column `lane`; the four partial sums meet in a fixed tree after the loop
-  const bool do_cs = AK && a.colsum != nullptr && tn == 0;
-  float cs = 0.f;
-  auto body = [&](auto pc, int kt) {
-    constexpr int P = decltype(pc)::value;
-    const int kn = (kt + 2 < nk ? kt + 2 : nk - 1) * GBK;  // the last iterations re-read the last tile
-    op_load<AK>(a.A, a.lda, tm * 64, a.M, kn, t, ra[P]);
-    op_load<BK>(a.B, a.ldb, tn * 64, a.N, kn, t, rb[P]);
-    __builtin_amdgcn_sched_barrier(0);  // the prefetch stays ahead of the MFMA block
-    const float* As = smem + P * GSTAGE;
-    const float* Bs = As + GOP;
-    float fa[16], fb[16];
-    op_frag<AK>(As, wm, li, lh, fa);
-    op_frag<BK>(Bs, wn, li, lh, fb);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q], fb[q], acc, 0, 0, 0);
-    if (AK && do_cs) {
-      const int left = a.cs_rows - kt * GBK - wave * 8;
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = As[(wave * 8 + q) * 64 + (lane ^ ((wave >> 1) << 5))];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) cs += q < left ? v[q] : 0.f;
-    }
-    float* nxt = smem + (P ^ 1) * GSTAGE;
-    op_store<AK>(nxt, t, ra[P ^ 1]);
-    op_store<BK>(nxt + GOP, t, rb[P ^ 1]);
-    __syncthreads();
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    body(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < nk) body(std::integral_constant<int, 1>{}, kt + 1);
-  }
-  // C/D map of the 32x32 f32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-  const int col = tn * 64 + wn * 32 + li;
-  if (col < a.N) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = tm * 64 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      float v = acc[e];
-      if (a.mask) {
-        const int mr = a.mask_mod ? row % a.mask_mod : row;
-        v = a.mask[(long long)mr * a.ldm + col] > 0.f ? v : 0.f;
-      }
-      a.C[(long long)row * a.ldc + col] = v;
-    }
-  }
-  if (AK && do_cs) {  // (the loop's last barrier is behind every read of smem)
-    smem[wave * 64 + lane] = cs;
-    __syncthreads();
-    if (wave == 0) a.colsum[tm * 64 + lane] = (smem[lane] + smem[64 + lane]) + (smem[128 + lane] + smem[192 + lane]);
-  }
-}
-
-template <int AK, int BK>
-int launch_gemm(const GemmArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((k_dfit_gemm<AK, BK>), dim3((a.N + 63) / 64, a.M / 64), dim3(256), 0, st, a);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
-}
-
-int check_gemm(const char* fn, const amx_ctx* ctx, const GemmArgs& a, int a_cols, int b_cols) {
-  AMX_CHECK_ARG(ctx, "%s: null ctx", fn);
-  AMX_CHECK_ARG(a.M > 0 && a.M % 64 == 0, "%s: M=%d must be a positive multiple of 64", fn, a.M);
-  AMX_CHECK_ARG(a.N > 0 && a.N % 4 == 0, "%s: N=%d must be a positive multiple of 4", fn, a.N);
-  AMX_CHECK_ARG(a.K > 0 && a.K % GBK == 0, "%s: the reduction length %d must be a positive multiple of %d", fn, a.K,
-                GBK);
-  AMX_CHECK_ARG(a.A && a.B && a.C && amx::aligned16(a.A) && amx::aligned16(a.B), "%s: null/unaligned operand", fn);
-  AMX_CHECK_ARG(a.lda >= a_cols && a.lda % 4 == 0 && a.ldb >= b_cols && a.ldb % 4 == 0 && a.ldc >= a.N,
-                "%s: lda=%d (>= %d) ldb=%d (>= %d) must be multiples of 4, ldc=%d (>= %d)", fn, a.lda, a_cols, a.ldb,
-                b_cols, a.ldc, a.N);
-  AMX_CHECK_ARG(!a.mask || (a.ldm >= a.N && a.mask_mod >= 0), "%s: ldm=%d mask_mod=%d", fn, a.ldm, a.mask_mod);
-  return AMX_OK;
-}
-
-// ---- the step's own kernels --------------------------------------------------------------
-
-constexpr int DF_NB_REG = 64;   // workgroups of k_dfit_reg
-constexpr int DF_CONST = 16;    // floats of the step constants
-constexpr int DF_T = 6;         // W0, b0, W1, b1, w2, b2
-
-struct StepConst {
-  float step, bc2s, omb1, b2, omb2, eps;  // Adam
-  float lr, mu;                           // SGD
-};
-static_assert(sizeof(StepConst) <= DF_CONST * sizeof(float), "step constants");
-
-struct Tensors {
-  float* w[DF_T];
-  long long off[DF_T + 1];  // offsets in the flat gradient / state vectors
-};
+constexpr int DF_NB_REG = amx::SUMSQ_NB;        // partial sums of the regularizer
+constexpr int DF_CONST = amx::STEP_CONST_FLOATS;  // floats of the step constants
+constexpr int DF_T = 6;                         // W0, b0, W1, b1, w2, b2
 
 struct Plan {
   int Dp, H0p, H1p;
@@ -261,17 +89,10 @@ __global__ __launch_bounds__(128) void k_dfit_gather(int bs, int Bt, int D, int 
   if (rl < bs) {
     const int32_t* idx = half ? idx_m : idx_e;
     const int n = half ? n_a : n_e;
-    int i = idx ? idx[rl] : rl;
-    i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+    const int i = amx::clamp_row(idx ? idx[rl] : rl, n);
     src = half ? agent + i * lda : expert + i * lde;
   }
   for (int c = threadIdx.x; c < Dp; c += 128) x[c] = (src && c < D) ? src[c] : 0.f;
-}
-
-__device__ inline float wave_sum(float s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  return s;
 }
 
 // one wave per row of H1 = [h1_e | h1_m]: out = h1 . w2 + b2, d out by loss type (ce, cm: the
@@ -307,32 +128,6 @@ __global__ __launch_bounds__(256) void k_dfit_head(int ls, int bs, int Bt, int H
   }
 }
 
-// partial sums of sum 1/2 W^2 over W0, W1, w2 (the padding is zero)
-__global__ __launch_bounds__(256) void k_dfit_reg(const float* __restrict__ W0, long long n0,
-                                                  const float* __restrict__ W1, long long n1,
-                                                  const float* __restrict__ w2, long long n2,
-                                                  double* __restrict__ part) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x;
-  const float* T[3] = {W0, W1, w2};
-  const long long n[3] = {n0 / 4, n1 / 4, n2 / 4};
-  double acc = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    const float4* p = (const float4*)T[k];
-    for (long long e = (long long)blockIdx.x * 256 + tid; e < n[k]; e += (long long)DF_NB_REG * 256) {
-      const float4 v = p[e];
-      acc += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-    }
-  }
-  red[tid] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) part[blockIdx.x] = 0.5 * red[0];
-}
-
 // one wave per expert row: |g|_2 and U = coef g / |g| (0 for rows >= bs and where |g| = 0,
 // as torch's norm backward)
 __global__ __launch_bounds__(256) void k_dfit_unit(int bs, int Dp, float coef, const float* __restrict__ G,
@@ -359,6 +154,7 @@ __global__ __launch_bounds__(1024) void k_dfit_gw2(int Bt, int H1p, const float*
   for (int r = ph; r < Bt; r += 16) s += P1[(long long)r * H1p + c];
   red[ph][lc] = s;
   __syncthreads();
+  // (a tree of its own: fp32, over the 16 row phases of each column, not amx::block_sum's fp64 over threads)
   for (int o = 8; o > 0; o >>= 1) {
     if (ph < o) red[ph][lc] += red[ph + o][lc];
     __syncthreads();
@@ -396,13 +192,8 @@ __global__ __launch_bounds__(256) void k_dfit_prep(int ls, int bs, int Bt, int a
   }
   for (int b = tid; b < DF_NB_REG; b += 256) v[5] += part[b];
   for (int k = 0; k < 7; ++k) {
-    red[tid] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) tot[k] = red[0];
+    const double s = amx::block_sum<256>(red, v[k]);
+    if (tid == 0) tot[k] = s;
     __syncthreads();
   }
   if (tid != 0) return;
@@ -419,98 +210,18 @@ __global__ __launch_bounds__(256) void k_dfit_prep(int ls, int bs, int Bt, int a
   metrics[7] = (double)t;
   gb2[0] = (float)tot[6];
   gb2[1] = gb2[2] = gb2[3] = 0.f;
-  StepConst s = {};
+  amx::StepConst s = {};
+  s.coef = 1.f;  // no clipping
   if (adam) {
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    s.step = (float)(lr / bc1);
-    s.bc2s = (float)sqrt(bc2);
-    s.omb1 = (float)(1.0 - b1);
-    s.b2 = (float)b2;
-    s.omb2 = (float)(1.0 - b2);
-    s.eps = (float)p1;
+    s.adam = amx::AdamConst(t, lr, 0.9, 0.999, p1);
   } else {
     s.lr = (float)lr;
     s.mu = (float)p1;
   }
-  *(StepConst*)cst = s;
-}
-
-// torch.optim.Adam's single-tensor update, op for op (k_efit_update's adam1)
-__device__ inline void adam1(float& w, float& m, float& v, float g, const StepConst& a) {
-  m = m + (g - m) * a.omb1;
-  v = v * a.b2 + (a.omb2 * g) * g;
-  const float den = sqrtf(v) / a.bc2s + a.eps;
-  w = w - a.step * (m / den);
-}
-
-// torch.optim.SGD, momentum, no Nesterov, dampening 0: buf = mu buf + g (the first step's zero
-// buffer gives g exactly); p -= lr buf
-__device__ inline void sgd1(float& w, float& buf, float g, const StepConst& a) {
-  buf = buf * a.mu + g;
-  w = w - a.lr * buf;
-}
-
-__global__ __launch_bounds__(256) void k_dfit_update(Tensors T, int adam, const float* __restrict__ grad,
-                                                     float* __restrict__ s1, float* __restrict__ s2,
-                                                     const float* __restrict__ cst) {
-  const StepConst a = *(const StepConst*)cst;
-  const long long gs = (long long)gridDim.x * 256;
-  for (int t = 0; t < DF_T; ++t) {
-    const long long n4 = (T.off[t + 1] - T.off[t]) / 4;
-    float4* w = (float4*)T.w[t];
-    const float4* gr = (const float4*)(grad + T.off[t]);
-    float4* m = (float4*)(s1 + T.off[t]);
-    float4* v = (float4*)(s2 + T.off[t]);
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n4; e += gs) {
-      const float4 gg = gr[e];
-      float4 ww = w[e], mm = m[e];
-      if (adam) {
-        float4 vv = v[e];
-        adam1(ww.x, mm.x, vv.x, gg.x, a);
-        adam1(ww.y, mm.y, vv.y, gg.y, a);
-        adam1(ww.z, mm.z, vv.z, gg.z, a);
-        adam1(ww.w, mm.w, vv.w, gg.w, a);
-        v[e] = vv;
-      } else {
-        sgd1(ww.x, mm.x, gg.x, a);
-        sgd1(ww.y, mm.y, gg.y, a);
-        sgd1(ww.z, mm.z, gg.z, a);
-        sgd1(ww.w, mm.w, gg.w, a);
-      }
-      w[e] = ww;
-      m[e] = mm;
-    }
-  }
+  *(amx::StepConst*)cst = s;
 }
 
 }  // namespace
-
-extern "C" int amx_gemm_nn_f32(amx_ctx* ctx, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                               float* C, int ldc, const float* mask, int ldm, int mask_mod, void* stream) {
-  GemmArgs a = {};
-  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
-  a.mask = mask; a.ldm = ldm; a.mask_mod = mask_mod;
-  a.M = M; a.N = N; a.K = K;
-  const int rc = check_gemm("amx_gemm_nn_f32", ctx, a, K, N);
-  if (rc) return rc;
-  return launch_gemm<0, 1>(a, (hipStream_t)stream);
-}
-
-extern "C" int amx_gemm_tn_f32(amx_ctx* ctx, int R, int M, int N, const float* A, int lda, const float* B, int ldb,
-                               float* C, int ldc, const float* mask, int ldm, float* colsum, int colsum_rows,
-                               void* stream) {
-  GemmArgs a = {};
-  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
-  a.mask = mask; a.ldm = ldm; a.mask_mod = 0;
-  a.colsum = colsum; a.cs_rows = colsum_rows;
-  a.M = M; a.N = N; a.K = R;
-  const int rc = check_gemm("amx_gemm_tn_f32", ctx, a, M, N);
-  if (rc) return rc;
-  AMX_CHECK_ARG(!colsum || (colsum_rows >= 0 && colsum_rows <= R), "amx_gemm_tn_f32: colsum_rows=%d (R=%d)",
-                colsum_rows, R);
-  return launch_gemm<1, 1>(a, (hipStream_t)stream);
-}
 
 extern "C" long long amx_dfit_param_count(int Dp, int H0p, int H1p) {
   Plan p;
@@ -589,61 +300,65 @@ extern "C" int amx_dfit_step(amx_ctx* ctx, int loss_type, int optim, double lr, 
   hipLaunchKernelGGL(k_dfit_head, dim3(2 * Bt / 4), dim3(256), 0, st, ls, bs, Bt, H1p, ce, cm, H1, w2, b2, out, dout,
                      Z1);
   AMX_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_dfit_reg, dim3(DF_NB_REG), dim3(256), 0, st, W0, (long long)H0p * Dp, W1, (long long)H1p * H0p,
-                     w2, (long long)H1p, part);
-  AMX_CHECK_LAUNCH();
-  GemmArgs g = {};
+  amx::TensorList R = {};  // the regularizer sum 1/2 W^2 runs over the three weights
+  R.n = 3;
+  R.w[0] = W0; R.w[1] = W1; R.w[2] = w2;
+  R.off[1] = p.off[1] - p.off[0];
+  R.off[2] = R.off[1] + (p.off[3] - p.off[2]);
+  R.off[3] = R.off[2] + (p.off[5] - p.off[4]);
+  if ((rc = amx::sum_squares(R, 1, 0.5, part, st))) return rc;
+  amx::Gemm64Args g = {};
   // Z0 = (Z1 W1) * (h0 > 0); the a1 block takes the expert rows' h0
   g.A = Z1; g.lda = H1p; g.B = W1; g.ldb = H0p; g.C = Z0; g.ldc = H0p;
   g.mask = H0s; g.ldm = H0p; g.mask_mod = 2 * Bt;
   g.M = 3 * Bt; g.N = H0p; g.K = H1p;
-  if ((rc = launch_gemm<0, 1>(g, st))) return rc;
+  if ((rc = amx::gemm64_nn(g, st))) return rc;
   // g = a0 W0
-  g = GemmArgs{};
+  g = amx::Gemm64Args{};
   g.A = Z0 + 2LL * Bt * H0p; g.lda = H0p; g.B = W0; g.ldb = Dp; g.C = G; g.ldc = Dp;
   g.M = Bt; g.N = Dp; g.K = H0p;
-  if ((rc = launch_gemm<0, 1>(g, st))) return rc;
+  if ((rc = amx::gemm64_nn(g, st))) return rc;
   hipLaunchKernelGGL(k_dfit_unit, dim3(Bt / 4), dim3(256), 0, st, bs, Dp, (float)(grad_lambda / (2.0 * bs)), G, U,
                      norm);
   AMX_CHECK_LAUNCH();
   // q0 = (U W0^T) * (h0_e > 0)
-  g = GemmArgs{};
+  g = amx::Gemm64Args{};
   g.A = U; g.lda = Dp; g.B = W0; g.ldb = Dp; g.C = H0s + 2LL * Bt * H0p; g.ldc = H0p;
   g.mask = H0s; g.ldm = H0p;
   g.M = Bt; g.N = H0p; g.K = Dp;
-  if ((rc = launch_gemm<0, 0>(g, st))) return rc;
+  if ((rc = amx::gemm64_nt(g, st))) return rc;
   // P1 = (q0 W1^T) * (h1_e > 0)
-  g = GemmArgs{};
+  g = amx::Gemm64Args{};
   g.A = H0s + 2LL * Bt * H0p; g.lda = H0p; g.B = W1; g.ldb = H0p; g.C = P1; g.ldc = H1p;
   g.mask = H1; g.ldm = H1p;
   g.M = Bt; g.N = H1p; g.K = H0p;
-  if ((rc = launch_gemm<0, 0>(g, st))) return rc;
+  if ((rc = amx::gemm64_nt(g, st))) return rc;
   // gW1 = Z1^T H0s, gb1 = column sums of Z1's ordinary rows
-  g = GemmArgs{};
+  g = amx::Gemm64Args{};
   g.A = Z1; g.lda = H1p; g.B = H0s; g.ldb = H0p; g.C = grad + p.off[2]; g.ldc = H0p;
   g.colsum = grad + p.off[3]; g.cs_rows = 2 * Bt;
   g.M = H1p; g.N = H0p; g.K = 3 * Bt;
-  if ((rc = launch_gemm<1, 1>(g, st))) return rc;
+  if ((rc = amx::gemm64_tn(g, st))) return rc;
   // gW0 = Z0^T X, gb0
-  g = GemmArgs{};
+  g = amx::Gemm64Args{};
   g.A = Z0; g.lda = H0p; g.B = X; g.ldb = Dp; g.C = grad + p.off[0]; g.ldc = Dp;
   g.colsum = grad + p.off[1]; g.cs_rows = 2 * Bt;
   g.M = H0p; g.N = Dp; g.K = 3 * Bt;
-  if ((rc = launch_gemm<1, 1>(g, st))) return rc;
+  if ((rc = amx::gemm64_tn(g, st))) return rc;
   hipLaunchKernelGGL(k_dfit_gw2, dim3(H1p / 64), dim3(1024), 0, st, Bt, H1p, dout, H1, P1, grad + p.off[4]);
   AMX_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_dfit_prep, dim3(1), dim3(256), 0, st, ls, bs, Bt, optim == AMX_DFIT_ADAM, lr, p1, c, reg_coef,
                      grad_lambda, out, dout, norm, part, grad + p.off[5], step, cst, metrics);
   AMX_CHECK_LAUNCH();
-  Tensors T = {};
+  amx::TensorList T = {};
   float* w[DF_T] = {W0, b0, W1, b1, w2, b2};
+  T.n = DF_T;
   for (int i = 0; i < DF_T; ++i) {
     T.w[i] = w[i];
     T.off[i] = p.off[i];
   }
   T.off[DF_T] = p.off[DF_T];
-  hipLaunchKernelGGL(k_dfit_update, dim3(256), dim3(256), 0, st, T, optim == AMX_DFIT_ADAM, grad, state1,
-                     optim == AMX_DFIT_ADAM ? state2 : state1, cst);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
+  const bool adam = optim == AMX_DFIT_ADAM;
+  return amx::update_tensors(T, 1, adam ? amx::OPTIM_ADAM : amx::OPTIM_SGD, grad, state1, adam ? state2 : state1,
+                             p.off[DF_T], cst, st);
 }

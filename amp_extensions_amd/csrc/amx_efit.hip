@@ -3,16 +3,17 @@
 //
 //   k_efit_gather   x0 = [(s - mu_s)/sd_s, (a - mu_a)/sd_a, 0-pad] and the normalised target
 //                   ((s' - s) - mu_d)/sd_d of the batch's rows; rows >= n_b zero
-//   amx_gemm_bias_act[_t64] x (L + 1)   the forward on the fp32 master weights (f32 MFMA; 64 x 64
-//                   tiles while 128 x 128 ones would leave compute units idle)
+//   amx_gemm_bias_act[_t64] x (L + 1)   the forward on the fp32 master weights (f32 MFMA; the
+//                   64 x 64 tiles of amx_gemm64.hip while 128 x 128 ones would leave compute
+//                   units idle)
 //   k_efit_loss     dZ_L = 2 (pred - target)/(n_b S), the step's MSE into loss[g]
 //   per layer i = L .. 0:
 //     k_efit_wgrad  gW_i = dZ_i^T act, gb_i = column sums of dZ_i
 //     k_efit_dgrad  dact[:, hidden slices < i] (+)= dZ_i W_i; the tiles of slice i - 1, final
 //                   after this launch, write dZ_{i-1} = dact * (act > 0)
-//   k_efit_sumsq    per-workgroup partial sums of g^2 (grad_clip > 0)
+//   k_optim_sumsq   per-workgroup partial sums of g^2 (grad_clip > 0; amx_optim.hip)
 //   k_efit_prep     clip_grad_norm_'s coefficient, the step count and Adam's bias corrections
-//   k_efit_update   torch.optim.Adam / SGD(nesterov=True) on every padded tensor
+//   k_optim_update  torch.optim.Adam / SGD(nesterov=True) on every padded tensor (amx_optim.hip)
 //
 // Stream order is the only synchronisation: no workgroup waits on another.  Every sum runs in
 // a fixed order, so a fit is deterministic.  The backward products are fp32 FMA chains on the
@@ -20,29 +21,14 @@
 // Zero-padded weights see a zero gradient, so they and their optimizer state stay exactly 0.
 #include <math.h>
 
-#include "amx_common.h"
+#include "amx_optim.h"
 
 namespace {
 
 constexpr int EF_MAX_LAYERS = 8;           // L + 1
-constexpr int EF_MAX_T = 2 * EF_MAX_LAYERS;  // weight and bias tensors
-constexpr int EF_NB_SQ = 64;               // workgroups per member of k_efit_sumsq
-constexpr int EF_CONST = 16;               // floats of a member's step constants
-
-// a member's step constants (k_efit_prep -> k_efit_update)
-struct StepConst {
-  float coef;                                   // clip_grad_norm_'s clip_coef_clamped
-  float step, bc2s, omb1, b2, omb2, eps;        // Adam
-  float lr, mu;                                 // SGD
-};
-static_assert(sizeof(StepConst) <= EF_CONST * sizeof(float), "step constants");
-
-struct Tensors {
-  float* w[EF_MAX_T];            // member 0's tensor
-  long long stride[EF_MAX_T];    // member stride of w
-  long long off[EF_MAX_T + 1];   // offsets in the flat gradient / state vectors
-  int n;
-};
+static_assert(2 * EF_MAX_LAYERS <= amx::OPTIM_MAX_T, "weight and bias tensors of the update's list");
+constexpr int EF_NB_SQ = amx::SUMSQ_NB;    // partial sums of g^2 per member
+constexpr int EF_CONST = amx::STEP_CONST_FLOATS;  // floats of a member's step constants
 
 struct Plan {
   int M, L, Hp, k0, ldk, NO, S, A;
@@ -104,8 +90,7 @@ __global__ __launch_bounds__(256) void k_efit_gather(int n_b, int n_rows, const 
     for (int c = threadIdx.x; c < NO; c += 256) t[c] = 0.f;
     return;
   }
-  int i = idx[g * strideIdx + r];
-  i = i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
+  const int i = amx::clamp_row(idx[g * strideIdx + r], n_rows);
   const float* s = states + (long long)i * S;
   const float* a = actions + (long long)i * A;
   const float* s2 = next_states + (long long)i * S;
@@ -118,94 +103,6 @@ __global__ __launch_bounds__(256) void k_efit_gather(int n_b, int n_rows, const 
     x[c] = v;
   }
   for (int c = threadIdx.x; c < NO; c += 256) t[c] = c < S ? ((s2[c] - s[c]) - mu_d[c]) / sd_d[c] : 0.f;
-}
-
-// The forward GEMM of amx_gemm.hip's k_gemm_nt (C = act(A W^T + b) on v_mfma_f32_32x32x2_f32,
-// K-tiles of 32 double-buffered in LDS, one barrier per K-tile) on 64 x 64 tiles: four waves of
-// one 32 x 32 block each.  Every output element runs the same K chain as in the 128 x 128 tile
-// (lanes 0-31 supply k, lanes 32-63 k + 16 of each K-tile), so the results are bit-identical; a
-// training step's few hundred rows give four times the workgroups.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int FBK = 32, FLD = FBK + 4, FSTAGE = 128 * FLD;  // K-tile, floats per LDS row, floats per stage
-
-struct FwdArgs {
-  const float* A; long long strideA; int lda;
-  const float* W; long long strideW; int ldw;
-  const float* bias; long long strideBias;
-  float* C; long long strideC; int ldc, col_off;
-  int K, act;
-};
-
-__global__ __launch_bounds__(256, 2) void k_efit_fwd64(FwdArgs a) {
-  __shared__ __align__(16) float smem[2 * FSTAGE];
-  const int tn = blockIdx.x, tm = blockIdx.y, g = blockIdx.z;
-  const float* __restrict__ Ag = a.A + g * a.strideA + (long long)tm * 64 * a.lda;
-  const float* __restrict__ Wg = a.W + g * a.strideW + (long long)tn * 64 * a.ldw;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  // staging: float4 of row (t >> 3) + 32 j, column 4 (t & 7), of the A and the W tile
-  const int st_r = t >> 3, st_c = (t & 7) * 4;
-  const float* a_src = Ag + (long long)st_r * a.lda + st_c;
-  const float* w_src = Wg + (long long)st_r * a.ldw + st_c;
-  const long long a_step = 32LL * a.lda, w_step = 32LL * a.ldw;
-  float* const a_dst0 = smem + st_r * FLD + st_c;
-  float* const w_dst0 = smem + 64 * FLD + st_r * FLD + st_c;
-  f32x4 ra[2], rw[2];
-  f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  const int nk = a.K / FBK;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    ra[j] = *reinterpret_cast<const f32x4*>(a_src + j * a_step);
-    rw[j] = *reinterpret_cast<const f32x4*>(w_src + j * w_step);
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    *reinterpret_cast<f32x4*>(a_dst0 + j * 32 * FLD) = ra[j];
-    *reinterpret_cast<f32x4*>(w_dst0 + j * 32 * FLD) = rw[j];
-  }
-  __syncthreads();
-  const int a_off = (wm * 32 + li) * FLD + lh * 16;
-  const int w_off = 64 * FLD + (wn * 32 + li) * FLD + lh * 16;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    const int kn = (kt + 1 < nk ? kt + 1 : kt) * FBK;  // the last iteration re-reads its own tile
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      ra[j] = *reinterpret_cast<const f32x4*>(a_src + j * a_step + kn);
-      rw[j] = *reinterpret_cast<const f32x4*>(w_src + j * w_step + kn);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // the prefetch stays ahead of the MFMA block
-    const float* As = smem + cur * FSTAGE + a_off;
-    const float* Ws = smem + cur * FSTAGE + w_off;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const f32x4 fa = *reinterpret_cast<const f32x4*>(As + v * 4);
-      const f32x4 fb = *reinterpret_cast<const f32x4*>(Ws + v * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
-    }
-    const int nb = (cur ^ 1) * FSTAGE;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      *reinterpret_cast<f32x4*>(a_dst0 + nb + j * 32 * FLD) = ra[j];
-      *reinterpret_cast<f32x4*>(w_dst0 + nb + j * 32 * FLD) = rw[j];
-    }
-    __syncthreads();
-  }
-  // C/D map of the 32x32 f32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-  const int col = tn * 64 + wn * 32 + li;
-  const float bv = a.bias[g * a.strideBias + col];
-  float* Cg = a.C + g * a.strideC;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int row = tm * 64 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-    float v = acc[e] + bv;
-    if (a.act == AMX_ACT_RELU) v = (v < 0.f) ? 0.f : v;  // keeps NaN, as torch.relu
-    Cg[(long long)row * a.ldc + a.col_off + col] = v;
-  }
 }
 
 // nn.MSELoss (mean over n_b x S) and its gradient; one workgroup per member
@@ -228,13 +125,8 @@ __global__ __launch_bounds__(1024) void k_efit_loss(int n_b, int Bt, int S, int 
     }
     dzL[base + e] = z;
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) loss[g * strideLoss] = (float)(red[0] / cnt);
+  const double sum = amx::block_sum<1024>(red, acc);
+  if (tid == 0) loss[g * strideLoss] = (float)(sum / cnt);
 }
 
 // gW[n][k] = sum_r dz[r][n] act[r][k]: 64 x 64 tiles, 16 rows of the reduction staged at a
@@ -341,32 +233,13 @@ __global__ __launch_bounds__(256) void k_efit_dgrad(int Nred, int k0, int accumu
   }
 }
 
-__global__ __launch_bounds__(256) void k_efit_sumsq(const float* __restrict__ grad, long long P,
-                                                    double* __restrict__ part) {
-  __shared__ double red[256];
-  const int g = blockIdx.y, tid = threadIdx.x;
-  const float4* p = (const float4*)(grad + g * P);
-  double acc = 0.0;
-  for (long long e = (long long)blockIdx.x * 256 + tid; e < P / 4; e += (long long)EF_NB_SQ * 256) {
-    const float4 v = p[e];
-    acc += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-  }
-  red[tid] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) part[g * EF_NB_SQ + blockIdx.x] = red[0];
-}
-
 // per member: clip_grad_norm_'s coefficient (max_norm / (norm + 1e-6), clamped to 1), the step
 // count, Adam's bias corrections (beta^t in double)
 __global__ void k_efit_prep(int M, int adam, double lr, double p1, double grad_clip, const double* __restrict__ part,
                             long long* __restrict__ step, float* __restrict__ cst) {
   const int g = threadIdx.x;
   if (g >= M) return;
-  StepConst c = {};
+  amx::StepConst c = {};
   c.coef = 1.f;
   if (grad_clip > 0.0) {
     double s = 0.0;
@@ -378,99 +251,15 @@ __global__ void k_efit_prep(int M, int adam, double lr, double p1, double grad_c
   const long long t = step[g] + 1;
   step[g] = t;
   if (adam) {
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    c.step = (float)(lr / bc1);
-    c.bc2s = (float)sqrt(bc2);
-    c.omb1 = (float)(1.0 - b1);
-    c.b2 = (float)b2;
-    c.omb2 = (float)(1.0 - b2);
-    c.eps = (float)p1;
+    c.adam = amx::AdamConst(t, lr, 0.9, 0.999, p1);
   } else {
     c.lr = (float)lr;
     c.mu = (float)p1;
   }
-  *(StepConst*)(cst + g * EF_CONST) = c;
-}
-
-// torch.optim.Adam's single-tensor update, op for op (amx_vfit.hip's adam_math without decay)
-__device__ inline void adam1(float& w, float& m, float& v, float g, const StepConst& a) {
-  m = m + (g - m) * a.omb1;
-  v = v * a.b2 + (a.omb2 * g) * g;
-  const float den = sqrtf(v) / a.bc2s + a.eps;
-  w = w - a.step * (m / den);
-}
-
-// torch.optim.SGD, momentum, nesterov, dampening 0: buf = mu buf + g (the first step's zero
-// buffer gives g exactly); p -= lr (g + mu buf)
-__device__ inline void sgd1(float& w, float& buf, float g, const StepConst& a) {
-  buf = buf * a.mu + g;
-  w = w - a.lr * (g + a.mu * buf);
-}
-
-__global__ __launch_bounds__(256) void k_efit_update(Tensors T, int adam, const float* __restrict__ grad,
-                                                     float* __restrict__ s1, float* __restrict__ s2, long long P,
-                                                     const float* __restrict__ cst) {
-  const int g = blockIdx.y;
-  const StepConst a = *(const StepConst*)(cst + g * EF_CONST);
-  const long long gs = (long long)gridDim.x * 256;
-  for (int t = 0; t < T.n; ++t) {
-    const long long n4 = (T.off[t + 1] - T.off[t]) / 4;
-    float4* w = (float4*)(T.w[t] + g * T.stride[t]);
-    const float4* gr = (const float4*)(grad + g * P + T.off[t]);
-    float4* m = (float4*)(s1 + g * P + T.off[t]);
-    float4* v = (float4*)(s2 + g * P + T.off[t]);
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n4; e += gs) {
-      float4 gg = gr[e], ww = w[e], mm = m[e];
-      gg = make_float4(gg.x * a.coef, gg.y * a.coef, gg.z * a.coef, gg.w * a.coef);
-      if (adam) {
-        float4 vv = v[e];
-        adam1(ww.x, mm.x, vv.x, gg.x, a);
-        adam1(ww.y, mm.y, vv.y, gg.y, a);
-        adam1(ww.z, mm.z, vv.z, gg.z, a);
-        adam1(ww.w, mm.w, vv.w, gg.w, a);
-        v[e] = vv;
-      } else {
-        sgd1(ww.x, mm.x, gg.x, a);
-        sgd1(ww.y, mm.y, gg.y, a);
-        sgd1(ww.z, mm.z, gg.z, a);
-        sgd1(ww.w, mm.w, gg.w, a);
-      }
-      w[e] = ww;
-      m[e] = mm;
-    }
-  }
+  *(amx::StepConst*)(cst + g * EF_CONST) = c;
 }
 
 }  // namespace
-
-extern "C" int amx_gemm_bias_act_t64(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
-                                     long long strideA, const float* W, int ldw, long long strideW,
-                                     const float* bias, long long strideBias, float* C, int ldc, long long strideC,
-                                     int col_off, int act, void* stream) {
-  const char* fn = "amx_gemm_bias_act_t64";
-  AMX_CHECK_ARG(ctx, "%s: null ctx", fn);
-  AMX_CHECK_ARG(groups >= 1 && groups <= AMX_MAX_MODELS, "%s: groups=%d", fn, groups);
-  AMX_CHECK_ARG(rows >= 0 && rows % AMX_ROW_TILE == 0, "%s: rows=%d must be a multiple of %d", fn, rows, AMX_ROW_TILE);
-  AMX_CHECK_ARG(K > 0 && K % AMX_K_TILE == 0, "%s: K=%d must be a positive multiple of %d", fn, K, AMX_K_TILE);
-  AMX_CHECK_ARG(A && W && amx::aligned16(A) && amx::aligned16(W), "%s: null/unaligned operand", fn);
-  AMX_CHECK_ARG(lda >= K && lda % 4 == 0 && ldw >= K && ldw % 4 == 0 && strideA % 4 == 0 && strideW % 4 == 0,
-                "%s: lda=%d ldw=%d (K=%d) must be >= K and, like the strides, multiples of 4", fn, lda, ldw, K);
-  AMX_CHECK_ARG(N > 0 && N % 64 == 0, "%s: N=%d must be a multiple of 64", fn, N);
-  AMX_CHECK_ARG(bias && C, "%s: null bias/C", fn);
-  AMX_CHECK_ARG(col_off >= 0 && col_off + N <= ldc, "%s: col_off=%d N=%d ldc=%d", fn, col_off, N, ldc);
-  AMX_CHECK_ARG(act == AMX_ACT_NONE || act == AMX_ACT_RELU, "%s: act=%d", fn, act);
-  if (rows == 0) return AMX_OK;
-  FwdArgs a = {};
-  a.A = A; a.strideA = strideA; a.lda = lda;
-  a.W = W; a.strideW = strideW; a.ldw = ldw;
-  a.bias = bias; a.strideBias = strideBias;
-  a.C = C; a.strideC = strideC; a.ldc = ldc; a.col_off = col_off;
-  a.K = K; a.act = act;
-  hipLaunchKernelGGL(k_efit_fwd64, dim3(N / 64, rows / 64, groups), dim3(256), 0, (hipStream_t)stream, a);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
-}
 
 extern "C" long long amx_efit_param_count(const amx_ctx* ctx) {
   Plan p;
@@ -568,13 +357,15 @@ extern "C" int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int
     sZ = sH;
   }
   if (grad_clip > 0.0) {
-    hipLaunchKernelGGL(k_efit_sumsq, dim3(EF_NB_SQ, M), dim3(256), 0, st, grad, p.P, part);
-    AMX_CHECK_LAUNCH();
+    amx::TensorList G = {};  // every member's flat gradient
+    G.n = 1;
+    G.w[0] = grad; G.stride[0] = p.P; G.off[1] = p.P;
+    if ((rc = amx::sum_squares(G, M, 1.0, part, st))) return rc;
   }
   hipLaunchKernelGGL(k_efit_prep, dim3(1), dim3(64), 0, st, M, optim == AMX_EFIT_ADAM, lr, p1, grad_clip, part, step,
                      cst);
   AMX_CHECK_LAUNCH();
-  Tensors T = {};
+  amx::TensorList T = {};
   T.n = 2 * (L + 1);
   for (int i = 0; i <= L; ++i) {
     const long long N = i == L ? NO : Hp, K = i == L ? ldk : k0 + (long long)i * Hp;
@@ -582,8 +373,6 @@ extern "C" int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int
     T.w[2 * i + 1] = b[i]; T.stride[2 * i + 1] = N; T.off[2 * i + 1] = p.offB[i];
   }
   T.off[T.n] = p.P;
-  hipLaunchKernelGGL(k_efit_update, dim3(256, M), dim3(256), 0, st, T, optim == AMX_EFIT_ADAM, grad, state1, state2,
-                     p.P, cst);
-  AMX_CHECK_LAUNCH();
-  return AMX_OK;
+  return amx::update_tensors(T, M, optim == AMX_EFIT_ADAM ? amx::OPTIM_ADAM : amx::OPTIM_SGD_NESTEROV, grad, state1,
+                             state2, p.P, cst, st);
 }

@@ -15,11 +15,7 @@
 
 namespace {
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+using amx::wave_sum;
 
 struct Grid {
   int T, L;

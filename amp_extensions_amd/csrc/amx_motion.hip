@@ -331,8 +331,7 @@ __device__ void motion_state(const MView& m, double time, int flags, double* __r
     // whole wave with independent loads (no dependent binary-search chain)
     int c = 0;
     for (int f = tid; f < m.F; f += 64) c += m.times[f] <= tt;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    c = amx::wave_sum(c);
     idx = c - 1;
     if (idx > m.F - 2) idx = m.F - 2;
     if (idx < 0) idx = 0;

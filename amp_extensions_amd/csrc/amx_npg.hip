@@ -61,6 +61,8 @@ __device__ unsigned long long npg_trace_buf[4][64];
 
 namespace {
 
+using amx::lds_barrier;
+
 constexpr int NH = 32;                 // hidden width (both layers)
 constexpr int RC0 = 32;                // rows per chunk (64-row chunks measured slower: DESIGN.md section 6)
 constexpr int NT = 512;                // threads per block: 8 waves, 2 per SIMD
@@ -84,7 +86,9 @@ constexpr int RCT = 1024, RCC = 64;  // k_npg_cg_reduce: threads, columns per bl
 constexpr int XRT = 1024;            // k_npg_cg_xrp threads (and elements owned) per block
 
 // the sum of n fixed-order parts, computed the same way by every wave that calls it (lane-strided
-// partial sums, then an xor butterfly: every lane ends with the same bits)
+// partial sums, then an xor butterfly: every lane ends with the same bits).  The butterfly runs
+// its offsets upwards, 1 to 32: another association than amx::wave_sum's, and these sums' bits
+// are pinned by the CG tests, so it stays its own loop.
 __device__ inline double parts_sum(const double* __restrict__ parts, int n) {
   const int lane = threadIdx.x & 63;
   double s = 0.0;
@@ -204,10 +208,6 @@ __device__ inline int small_dst(int e, const Geo& g) {  // offsets as carve_smal
   return o_ls + e;
 }
 
-// Workgroup barrier for LDS hand-offs: waits for this wave's LDS traffic only, so the next
-// chunk's global loads stay in flight across it (__syncthreads' fence waits for them too).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // The CG fold (amx_npg_pass_cg): the previous iteration's vector step -- k_npg_cg_xrp's
 // arithmetic in its orders, so the same bits -- at the head of the next Fisher-vector pass,
 // which drops that launch from every iteration but the last.  Every block forms v = r.r / p.z
@@ -255,11 +255,8 @@ __device__ __forceinline__ bool cg_fold(const NpgArgs& a, float* pb, int t) {
     rl[2 * u + 1] = rl[2 * u + 1] - v * zl[2 * u + 1];
     rr1 += rl[2 * u + 1] * rl[2 * u + 1];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    rr0 += __shfl_xor(rr0, o);
-    rr1 += __shfl_xor(rr1, o);
-  }
+  rr0 = amx::wave_sum(rr0);
+  rr1 = amx::wave_sum(rr1);
   double* red = reinterpret_cast<double*>(pb + r4(P));
   if ((t & 63) == 0) {
     red[t >> 6] = rr0;
@@ -967,8 +964,7 @@ __global__ void k_npg_reduce2(const double* __restrict__ mid, int nr, int P, dou
 // ---- conjugate gradient (cg_solve.py:3-23) ---------------------------------------------
 // sum over the workgroup in a fixed order (per-thread sums, wave butterflies, waves in order)
 __device__ double cg_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = amx::wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = 0.0;
@@ -1221,8 +1217,7 @@ __global__ __launch_bounds__(XRT) void k_npg_cg_xrp(int P, double tol, const dou
       rr += rv * rv;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rr += __shfl_xor(rr, o);
+  rr = amx::wave_sum(rr);
   if ((t & 63) == 0) red[t >> 6] = rr;
   __syncthreads();
   rr = 0.0;

@@ -30,7 +30,8 @@ __device__ __forceinline__ double dpp_f64(double v) {
 // 0 -> 1 and 2 -> 3 (row_bcast:15), rows 0+1 -> 2, 3 (row_bcast:31), lane 63 read back.  A fixed
 // association: every caller (the fused step, k_disagreement) gets the same bits for the same
 // lane values.  (The LDS-based __shfl_xor butterfly cost 5.7 us of the 8192-lane step kernel's
-// 21.4 for its six pair sums, tools/step_time.py.)
+// 21.4 for its six pair sums, tools/step_time.py; amx_common.h's amx::wave_sum is that butterfly,
+// another association, so this one stays.)
 __device__ inline double wave_sum(double v) {
   v += dpp_f64<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
   v += dpp_f64<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]

@@ -22,9 +22,10 @@
 // ([column][row], 64 rows), which keeps every global access of the chain coalesced.
 // Reductions run in a fixed order: the result is deterministic.  Zero-padded weights see a zero
 // gradient and no decay (wd * 0), so Adam leaves them, and their moments, exactly 0.
+// Adam's constants and update are amx_optim.h's (AdamConst, adam_apply); the decay is added here.
 #include <math.h>
 
-#include "amx_common.h"
+#include "amx_optim.h"
 
 namespace {
 
@@ -48,31 +49,15 @@ constexpr int W_DY = W_Y + VB;              // dy [VB]
 constexpr int W_XB = W_DY + VB;
 
 struct Adam {
-  float step, bc2s, omb1, b2, omb2, eps, wd;
+  amx::AdamConst c;
+  float wd;
 };
 static_assert(W_ADAM + sizeof(Adam) / sizeof(float) <= W_H0, "workspace header");
 
-__device__ inline Adam adam_consts(long long t, double lr, double b1, double b2, double eps, double wd) {
-  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-  Adam a;
-  a.step = (float)(lr / bc1);
-  a.bc2s = (float)sqrt(bc2);
-  a.omb1 = (float)(1.0 - b1);
-  a.b2 = (float)b2;
-  a.omb2 = (float)(1.0 - b2);
-  a.eps = (float)eps;
-  a.wd = (float)wd;
-  return a;
-}
-
-// torch.optim.Adam's single-tensor update, op for op: grad.add(p, alpha=wd); exp_avg.lerp_;
-// exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2); denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_.
+// torch.optim.Adam with weight decay: grad.add(p, alpha=wd), then amx_optim.h's update
 __device__ inline void adam_math(float& w, float& m, float& v, float g, const Adam& a) {
   g = g + a.wd * w;
-  m = m + (g - m) * a.omb1;
-  v = v * a.b2 + (a.omb2 * g) * g;
-  const float den = sqrtf(v) / a.bc2s + a.eps;
-  w = w - a.step * (m / den);
+  amx::adam_apply(w, m, v, g, a.c);
 }
 
 __device__ inline void adam_update(float* w, float* m, float* v, float g, const Adam& a) {
@@ -81,12 +66,6 @@ __device__ inline void adam_update(float* w, float* m, float* v, float g, const 
   *w = w1;
   *m = m1;
   *v = v1;
-}
-
-__device__ inline float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // y^ from the head partials in workgroup order, then d = y^ - y (one thread per batch row)
@@ -100,8 +79,7 @@ __device__ inline float batch_residual(const float* __restrict__ work, const flo
 // rows of mini-batch mb; an index outside [0, n_rows) is clamped (callers validate perm)
 __device__ inline void batch_rows(int* sidx, const int32_t* __restrict__ perm, int mb, int n_rows) {
   if (threadIdx.x < VB) {
-    int i = perm[(long long)mb * VB + threadIdx.x];
-    sidx[threadIdx.x] = i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
+    sidx[threadIdx.x] = amx::clamp_row(perm[(long long)mb * VB + threadIdx.x], n_rows);
   }
 }
 
@@ -189,9 +167,7 @@ __global__ __launch_bounds__(256) void k_vfit_l1(int mb, int n_rows, const float
 #pragma unroll
   for (int i = 0; i < 8; ++i) rw[i] = W1[(c0 + (tid >> 7) + 2 * i) * VH + (tid & 127)];
   if (blockIdx.x == 0 && tid < VB) {  // the batch's targets, for k_vfit_bwd
-    int i = perm[(long long)mb * VB + tid];
-    i = i < 0 ? 0 : (i >= n_rows ? n_rows - 1 : i);
-    work[W_Y + tid] = returns[i];
+    work[W_Y + tid] = returns[amx::clamp_row(perm[(long long)mb * VB + tid], n_rows)];
   }
 #pragma unroll
   for (int i = 0; i < 32; ++i) s.a[r][cg + 4 * i] = ra[i];
@@ -230,14 +206,14 @@ __global__ __launch_bounds__(256) void k_vfit_bwd(const float* __restrict__ W1, 
     if (tid < VB) {
       const float d = batch_residual(work, b2, tid);
       work[W_DY + tid] = (2.f * d) * (1.f / VB);
-      const float loss = wave_sum_f(d * d) * (1.f / VB);
+      const float loss = amx::wave_sum(d * d) * (1.f / VB);
       if (tid == 0) {
         const float ls = work[W_LOSS] + loss;
         work[W_LOSS] = ls;
         epoch_loss[0] = ls / (float)num_steps;
         const long long t = adam_step[0] + 1;
         adam_step[0] = t;
-        *(Adam*)(work + W_ADAM) = adam_consts(t, lr, beta1, beta2, eps, wd);  // beta^t in double
+        *(Adam*)(work + W_ADAM) = Adam{amx::AdamConst(t, lr, beta1, beta2, eps), (float)wd};  // beta^t in double
       }
     }
     return;
@@ -375,10 +351,10 @@ __global__ __launch_bounds__(256) void k_vfit_adam(int kf, float* __restrict__ W
   }
   // lane i of the wave updates the wave's entry i (every lane holds every sum): one memory round
   // trip for the 12 entries, not one each; lane 12 of the first wave of workgroup NW0 takes b2
-  float g = wave_sum_f(dy);
+  float g = amx::wave_sum(dy);
 #pragma unroll
   for (int i = 0; i < 3 * VT / 4; ++i) {
-    const float s = wave_sum_f(gb[i]);
+    const float s = amx::wave_sum(gb[i]);
     if (lane == i) g = s;
   }
   float* pw = nullptr;

@@ -14,11 +14,12 @@ rows = sorted(csv.DictReader(open(path)), key=lambda x: int(x["Start_Timestamp"]
 
 
 def short(name):
-    return name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0][:44]
+    name = name.replace("(anonymous namespace)::", "").replace("void ", "").replace("(amx::OptimKind)", "kind ")
+    return name.replace("amx::", "").split("(")[0][:44]
 
 
 gathers = [i for i, x in enumerate(rows) if "k_dfit_gather" in x["Kernel_Name"]]
-last = max(i for i, x in enumerate(rows) if "k_dfit_update" in x["Kernel_Name"])
+last = max(i for i, x in enumerate(rows) if "k_optim_update" in x["Kernel_Name"])  # a step's last launch
 end = last + 1
 while end < len(rows) and ("k_split" in rows[end]["Kernel_Name"] or "copyBuffer" in rows[end]["Kernel_Name"]):
     end += 1
@@ -41,6 +42,6 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
           f"{100 * sum(v) / tot:5.1f}")
 print("\nper launch shape (workgroups x, y, z; calls; avg us):")
 for (k, wg), v in sorted(shapes.items()):
-    if "dfit" in k or "efit_fwd64" in k:
+    if "dfit" in k or "gemm64" in k or "optim" in k:
         print(f"{k:44s} {wg[0]:4d} x {wg[1]:3d} x {wg[2]:2d} {len(v):6d} {sum(v) / len(v):8.2f}")
 print(f"\nsum of kernel time per step: {tot / K:.1f} us; span of the {K} steps per step: {span / K:.1f} us")
