@@ -677,7 +677,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
     // un-scale in place (exact powers of two) while sExp (in the stage area) is readable
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
-      const int4 ev = *reinterpret_cast<const int4*>(sExp + lrow0 + m * 16 + 4 * lq);
+      const int4 ev = *reinterpret_cast<const int4*>(sExp + TL::exp_word(lrow0 + m * 16 + 4 * lq));
 #pragma unroll
       for (int n = 0; n < NB; ++n) {
         const int ec = wexp[col0 + n * 16 + lc] - 2 * HSC;
@@ -736,7 +736,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
     uint32_t mx[MB * 4];
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
-      const int4 ev = *reinterpret_cast<const int4*>(sExp + lrow0 + m * 16 + 4 * lq);
+      const int4 ev = *reinterpret_cast<const int4*>(sExp + TL::exp_word(lrow0 + m * 16 + 4 * lq));
       const int er[4] = {ev.x, ev.y, ev.z, ev.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) mx[m * 4 + j] = 0u;
@@ -756,6 +756,19 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
     }
     if (a.row_exp_out) {
       int* out = a.row_exp_out + (long long)g * a.strideRexp;
+      // The tile's WN waves of a row first meet in LDS (the padding words of buffer 1: free of
+      // the K loop's traffic, so no barrier ahead of the writes), then one atomicMax per row and
+      // workgroup -- the same maximum as one per wave.
+      constexpr bool WGRED = TL::WN > 1;
+      static_assert(TL::WN * TL::BM < TL::PAD_WORDS, "row maxima in buffer 1's padding");
+      extern __shared__ __attribute__((aligned(16))) float smem[];
+      uint32_t* red = reinterpret_cast<uint32_t*>(smem);
+      auto emit = [&](int lrow, uint32_t bits) {  // lrow: row within the wave's WROWS
+        if constexpr (WGRED)
+          red[TL::pad_word(1, wn * TL::BM + lrow0 + lrow)] = bits;
+        else
+          atomicMax(out + row0 + lrow, exp_of_bits(bits));
+      };
       if constexpr (MB * 4 == 16 || MB * 4 == 32) {
         // reduce-scatter over the 16 column lanes (bits 3..0 of lc): lane lc keeps the PER
         // values of flat indices PER*lc .. PER*lc+PER-1 (flat index = m*4 + j)
@@ -767,7 +780,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
           const int i = PER * lc + u, m = i >> 2, j = i & 3;
-          atomicMax(out + row0 + m * 16 + 4 * lq + j, exp_of_bits(mx[u]));
+          emit(m * 16 + 4 * lq + j, mx[u]);
         }
       } else {
         // any MB: per 16-row block, reduce-scatter the lane's 4 row values over lc bits 3, 2
@@ -782,7 +795,19 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
           o = (uint32_t)__builtin_amdgcn_ds_swizzle((int)q4[0], 0x1f | (1 << 10));
           q4[0] = q4[0] > o ? q4[0] : o;
           if ((lc & 3) == 0)
-            atomicMax(out + row0 + m * 16 + 4 * lq + ((lc >> 3) & 1) * 2 + ((lc >> 2) & 1), exp_of_bits(q4[0]));
+            emit(m * 16 + 4 * lq + ((lc >> 3) & 1) * 2 + ((lc >> 2) & 1), q4[0]);
+        }
+      }
+      if constexpr (WGRED) {
+        __syncthreads();
+        for (int r = threadIdx.x; r < TL::BM; r += TL::NT) {
+          uint32_t b = red[TL::pad_word(1, r)];
+#pragma unroll
+          for (int w = 1; w < TL::WN; ++w) {
+            const uint32_t o = red[TL::pad_word(1, w * TL::BM + r)];
+            b = b > o ? b : o;
+          }
+          atomicMax(out + tm * TL::BM + r, exp_of_bits(b));
         }
       }
     }
@@ -796,7 +821,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
         const int ec = wexp[col] - 2 * HSC;
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
-          const int4 ev = *reinterpret_cast<const int4*>(sExp + lrow0 + m * 16 + 4 * lq);
+          const int4 ev = *reinterpret_cast<const int4*>(sExp + TL::exp_word(lrow0 + m * 16 + 4 * lq));
           const int er[4] = {ev.x, ev.y, ev.z, ev.w};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -822,7 +847,7 @@ __device__ __forceinline__ void gather_row_exps(const GemmArgs& a, int g, int tm
       const int v = re[s * slot + r];
       e = v > e ? v : e;
     }
-    sExp[r] = e;
+    sExp[TL::exp_word(r)] = e;
   }
 }
 
@@ -1000,7 +1025,7 @@ __device__ __forceinline__ void h3_tile_m16(const GemmArgs& a, int tile, int kb,
   constexpr int NT = TL::NT, STAGE = TL::STAGE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   uint16_t* const sm = reinterpret_cast<uint16_t*>(smem);
-  int* sExp = reinterpret_cast<int*>(sm + TL::SEXP);  // in stage buffer 1 until the loop's first publish
+  int* sExp = reinterpret_cast<int*>(smem);  // words TL::exp_word(r): they stay through the K loop
   int g, tm, tn;
   tile_coords(a, tile, g, tm, tn);
   const float* __restrict__ Ag = a.A + (long long)g * a.strideA + (long long)tm * BM * a.lda;
@@ -1034,7 +1059,7 @@ __device__ __forceinline__ void h3_tile_m16(const GemmArgs& a, int tile, int kb,
     const int r = a_ok[j] ? q / CPR : 0, c = q % CPR;
     a_src[j] = r * a.lda + 4 * c;
     a_dst[j] = r * LD + (c >> 2) * 32 + (c & 3) * 4;
-    a_sh[j] = HSC - sExp[r];
+    a_sh[j] = HSC - sExp[TL::exp_word(r)];
   }
   int w_off_b[VW];  // byte offsets from the tile's first weight row
   int w_dst[VW];
@@ -1222,15 +1247,13 @@ __device__ __forceinline__ void h3_tile_m16(const GemmArgs& a, int tile, int kb,
   // registers it cannot spare)
   if constexpr (EPI == EPI_UNNORM || (EPI == EPI_BIAS_ACT && !(BM == 256 && TL::BN == 256))) {
     if (nseg > 1) {
-      __syncthreads();  // the stage buffers are free: one int of LDS for the last-arriver flag
-      if (!split_combine<TL>(a, acc, tile, seg, nseg, reinterpret_cast<int*>(smem) + BM + 4)) return;
+      // the last-arriver flag: the last padding word of buffer 1 (clear of the row exponents and
+      // of the epilogue's row maxima)
+      if (!split_combine<TL>(a, acc, tile, seg, nseg,
+                             reinterpret_cast<int*>(smem) + TL::pad_word(1, TL::PAD_WORDS - 1)))
+        return;
     }
   }
-  // the row exponents lived in stage buffer 1 during the prologue; re-read them into LDS
-  __syncthreads();
-  sExp = reinterpret_cast<int*>(sm);
-  gather_row_exps<TL>(a, g, tm, sExp);
-  __syncthreads();
   epilogue_h3_m16<EPI, TL>(a, acc, sExp, g, tm, tn);
 #if H3_TRACE
   H3_STAMP(a, 4);
