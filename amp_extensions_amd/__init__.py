@@ -6,8 +6,8 @@ reward and the humanoid3d fall/horizon termination, as hand-written HIP kernels 
 gfx950 behind a C ABI (include/amx_hip.h, libamx_hip.so) and the reference's Python
 surfaces (SimEnv, sample_points, RBFLinearCost, GAILCost, DynamicsEnsemble), plus the
 sampler's consumers: returns, MLP value baseline (prediction and the mini-batch Adam fit) and
-GAE (mjrl process_samples, MLPBaseline), the NPG policy update (mjrl npg_cg) and the
-behaviour-cloning warm start (mjrl BC).
+GAE (mjrl process_samples, MLPBaseline), the NPG and PPO policy updates (mjrl npg_cg, ppo_clip)
+and the behaviour-cloning warm start (mjrl BC).
 
 The native library is loaded on first use; there is no CPU fallback.
 """
@@ -17,6 +17,7 @@ __all__ = [
     "AmxContext", "DeviceEnsemble", "RffMap", "RolloutEngine", "RBFLinearCost", "GAILCost", "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
     "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
+    "PPO", "DevicePPO",
 ]
 
 
@@ -48,6 +49,9 @@ def __getattr__(name):
     if name in ("BC", "DeviceBC", "plan_bc_batches"):
         from . import bc
         return getattr(bc, name)
+    if name in ("PPO", "DevicePPO"):
+        from . import ppo
+        return getattr(ppo, name)
     if name == "sample_points":
         from .sampler import sample_points
         return sample_points

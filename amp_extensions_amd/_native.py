@@ -157,6 +157,9 @@ SIGNATURES = {
     "amx_bcfit_steps": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, c_int, vp, vp, vp, vp, c_dbl, c_dbl, c_dbl, c_dbl,
                                 c_dbl, c_int, vp, vp]),
     "amx_bcfit_eval": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, c_int, vp, vp, vp]),
+    "amx_ppo_steps": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, vp, vp, c_int, vp, c_int, vp, vp, vp, vp, c_dbl, c_dbl,
+                              c_dbl, c_dbl, c_dbl, vp, vp, vp]),
+    "amx_ppo_old_ll": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, vp, vp]),
     "amx_philox":(c_int, [vp, c_u64, c_u32, c_u32, c_u32, vp, c_int, vp]),
     "amx_mt_seed": (c_int, [vp, c_int, vp, vp, c_int]),
     "amx_mt_policy_noise": (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_ll, c_ll]),
@@ -172,6 +175,7 @@ AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
 AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1
 AMX_DFIT_SGD, AMX_DFIT_ADAM = 0, 1
 AMX_BC_MSE, AMX_BC_MLE = 0, 1
+AMX_PPO_OLD_SNAPSHOT, AMX_PPO_OLD_TRACKS_MEAN = 0, 1
 
 
 class AmxNativeError(RuntimeError):

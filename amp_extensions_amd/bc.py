@@ -218,6 +218,30 @@ class DataLog:
         self.max_len = max(self.max_len, len(self.log[key]))
 
 
+def check_adam(optimizer) -> None:
+    """The optimizers the device fits implement: torch.optim.Adam, one group, no amsgrad / maximize."""
+    if type(optimizer) is not torch.optim.Adam:
+        raise NotImplementedError(f"the device fit implements torch.optim.Adam, not {type(optimizer).__name__}")
+    if len(optimizer.param_groups) != 1:
+        raise NotImplementedError("the device fit supports one parameter group")
+    g = optimizer.param_groups[0]
+    if g.get("amsgrad", False) or g.get("maximize", False):
+        raise NotImplementedError("the device fit implements Adam without amsgrad / maximize")
+
+
+def write_optimizer(optimizer, d) -> None:
+    """The device Adam state of `d` (adam_state, _trained) -> optimizer.state (step, exp_avg,
+    exp_avg_sq per trained parameter), so a later fit, here or on the host, resumes where this
+    one stopped."""
+    step, ms, vs = d.adam_state()
+    if step == 0:
+        return
+    params = optimizer.param_groups[0]["params"]
+    for p, m, v in list(zip(params, ms, vs))[:d._trained()]:
+        optimizer.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.to(p.device).view_as(p),
+                              "exp_avg_sq": v.to(p.device).view_as(p)}
+
+
 class BC:
     """mjrl's BC (behavior_cloning.py:14-145) with the fit on the device.  `policy`: an mjrl MLP
     or any object with its attribute layout (model.fc_layers, log_std, trainable_params,
@@ -241,13 +265,7 @@ class BC:
         if batch_size != BATCH:
             raise NotImplementedError(f"the device fit supports batch_size {BATCH}, not {batch_size}")
         if optimizer is not None:
-            if type(optimizer) is not torch.optim.Adam:
-                raise NotImplementedError(f"the device fit implements torch.optim.Adam, not {type(optimizer).__name__}")
-            if len(optimizer.param_groups) != 1:
-                raise NotImplementedError("the device fit supports one parameter group")
-            g = optimizer.param_groups[0]
-            if g.get("amsgrad", False) or g.get("maximize", False):
-                raise NotImplementedError("the device fit implements Adam without amsgrad / maximize")
+            check_adam(optimizer)
         self.policy = policy
         self.expert_paths = expert_paths
         self.epochs = epochs
@@ -276,17 +294,6 @@ class BC:
             float(hyper["eps"]), float(hyper["weight_decay"])
         return d
 
-    def _write_optimizer(self, d: DeviceBC) -> None:
-        """The device Adam state -> self.optimizer.state (step, exp_avg, exp_avg_sq per trained
-        parameter), so a later fit, here or on the host, resumes where this one stopped."""
-        step, ms, vs = d.adam_state()
-        if step == 0:
-            return
-        params = self.optimizer.param_groups[0]["params"]
-        for p, m, v in list(zip(params, ms, vs))[:d._trained()]:
-            self.optimizer.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.to(p.device).view_as(p),
-                                       "exp_avg_sq": v.to(p.device).view_as(p)}
-
     def fit(self, data, suppress_fit_tqdm=False, **kwargs):
         assert all(k in data.keys() for k in ["observations", "expert_actions"])
         ts = timer.time()
@@ -299,7 +306,7 @@ class BC:
         before, totals, after = d.fit(obs, act, self.epochs)
         for ep, total_loss in enumerate(totals):
             print(f"Total loss for epoch {ep}: {total_loss}")
-        self._write_optimizer(d)
+        write_optimizer(self.optimizer, d)
         params_after_opt = d.theta.cpu().numpy()
         self.policy.set_param_values(params_after_opt, set_new=True, set_old=True)
         clamped = self.policy.get_param_values()

@@ -41,6 +41,25 @@
 // k_bcfit_eval is the same forward over all N rows (BC.fit's loss_before / loss_after), 64 rows
 // at a time on as many workgroups as fill the chip: fp32 per row as the reference, fp64 per
 // workgroup, and k_bcfit_eval_sum adds the workgroups' partials in workgroup order.
+//
+// k_ppo_steps is the same step body (steps_body<true>) with PPO's clipped surrogate
+// (mjrl/mjrl/algos/ppo_clip.py:48-55, 88-97) in place of BC's loss: the MLE forward and
+// backward with a weight g_r on every row.  Its additions:
+//   gather  adv[row] and (snapshot mode) ll_old[row] travel with the batch (wave 15, lane = row)
+//   P2      waves 10 / 11 form sum log_std / sum log_std_old
+//   P3      each lane also squares its z, a butterfly adds the 16 columns of a tile, and the
+//           tile's partial goes to PN [CT][64]; in tracks-mean mode the same for
+//           z_old = (a - mu) / sigma_old into PO (mu is the step's own: the old mean network
+//           shares the new one's storage)
+//   P3b     wave 0, lane = row: LL_new and LL_old from the partials in tile order (row_ll; the
+//           snapshot's LL_old was formed by the same code in k_ppo_old_ll, so equal policies
+//           give LR = exp(0)), LR, g = adv LR pass -> G, the row's surrogate term -> SURR, the
+//           count of rows outside [lo, hi] by ballot -> step_clipped
+//   P4      D2, gW3, b3 and the log_std gradient take g_r as a factor of row r's Z; wave 15
+//           sums SURR into the step's loss
+// P5 - P7 and Adam are BC's.  BC's instantiation (steps_body<false>) compiles none of this in
+// and its LDS image ends ahead of PPO's fields.  k_ppo_old_ll is eval_body<true>: LL of every
+// row at theta.
 #include <math.h>
 
 #include "amx_optim.h"
@@ -65,7 +84,8 @@ typedef float pf4 __attribute__((ext_vector_type(4)));
 struct Lay {
   int S, A, KP, XS, A16, AS, CT, KT;
   int W1, W2, W3, b1, b2, b3, ls, X, ACT, H1, H2, D2, PART, SC, ADAM, IDX, total;
-  __host__ __device__ Lay(int S_, int A_) : S(S_), A(A_) {
+  int ADV, LLO, G, SURR, LSO, PN, PO, SL;  // PPO only
+  __host__ __device__ Lay(int S_, int A_, bool ppo = false) : S(S_), A(A_) {
     KP = (S + 15) / 16 * 16;
     XS = KP + 4 + (KP % 32 ? 16 : 0);  // = 4 mod 32
     A16 = (A + 15) / 16 * 16;
@@ -89,6 +109,17 @@ struct Lay {
     SC = o; o += MAXA;          // column scales of d mu
     ADAM = o; o += 8;
     IDX = o; o += 2 * BB;       // row indices of the next two steps (int)
+    ADV = LLO = G = SURR = LSO = PN = PO = SL = o;
+    if (ppo) {                  // BC's image ends above
+      ADV = o; o += BB;         // the batch's whitened advantages
+      LLO = o; o += BB;         // the batch's LL_old (snapshot mode)
+      G = o; o += BB;           // row weights g = adv LR pass
+      SURR = o; o += BB;        // rows' min(LR adv, clamp(LR) adv)
+      LSO = o; o += MAXA;       // log_std_old (tracks-mean mode) | zeros
+      PN = o; o += MAXA / 16 * BB;  // sum_c z^2 per column tile [CT][64]
+      PO = o; o += MAXA / 16 * BB;  // the same of z_old (tracks-mean mode)
+      SL = o; o += 8;           // sum log_std, sum log_std_old
+    }
     total = o;
   }
   __host__ __device__ size_t bytes() const { return (size_t)total * sizeof(float); }
@@ -158,6 +189,18 @@ __device__ __forceinline__ pf4 tile_tn(const float* __restrict__ a, int lda, con
   return acc;
 }
 
+// the same with row weights: sum over r of (A[r][ca] g[r]) B[r][cb]
+__device__ __forceinline__ pf4 tile_tn_w(const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb,
+                                         const float* __restrict__ g, int kq) {
+  pf4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int s = 0; s < 16; ++s) {
+    const int r = krow(s, kq);
+    acc = mma(a[r * lda] * g[r], b[r * ldb], acc);
+  }
+  return acc;
+}
+
 // The thread's indices, re-derived at every phase of a step from a thread id the compiler cannot
 // see through: otherwise it hoists every per-thread LDS address of the step out of the step
 // loop, which costs some 80 registers (spilled to scratch at 128 per thread) for a few integer
@@ -198,6 +241,47 @@ __device__ __forceinline__ float strided_sum(const float* __restrict__ p, int ld
   return s;
 }
 
+// the same over two arrays: sum of f(p[e * ld], q[e])
+template <typename F>
+__device__ __forceinline__ float strided_sum2(const float* __restrict__ p, int ld, const float* __restrict__ q, int n,
+                                              F f) {
+  float s = 0.f;
+#pragma unroll 1
+  for (int e0 = 0; e0 < n; e0 += 8) {
+    float v[8], w[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      v[u] = p[(e0 + u) * ld];
+      w[u] = q[e0 + u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += f(v[u], w[u]);
+  }
+  return s;
+}
+
+// sum over the 16 lanes that share lane >> 4, as a butterfly: every lane of the group gets the
+// same bits (a + b == b + a), in an order that depends on nothing but the lane numbers
+__device__ __forceinline__ float group16_sum(float v) {
+  v += __shfl_xor(v, 8);
+  v += __shfl_xor(v, 4);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 1);
+  return v;
+}
+
+// PPO's per-row log-likelihood, the one form of the step kernel and of k_ppo_old_ll (so a
+// ratio of equal policies is exp(0)): sum_c z^2 from P3's column-tile partials in tile order,
+// LL = (-0.5 sum z^2 - sum log_std) - 0.5 A log(2 pi) as gaussian_mlp.py:119-121 groups it
+__device__ __forceinline__ float sum_log_std(const float* __restrict__ ls, const Lay& L) {
+  return strided_sum(ls, 1, L.A16, [](float x) { return x; });  // zero past A
+}
+__device__ __forceinline__ float row_ll(const float* __restrict__ part, float sl, const Lay& L, int r) {
+  float s = 0.f;
+  for (int ct = 0; ct < L.CT; ++ct) s += part[ct * BB + r];
+  return (-0.5f * s - sl) - (float)(0.5 * (double)L.A * 1.8378770664093453);  // log(2 pi)
+}
+
 struct StepConsts {
   long long t;  // Adam's step count of this step (1-based)
   double lr, beta1, beta2, eps, wd;
@@ -205,8 +289,12 @@ struct StepConsts {
 
 // The forward of the 64 rows in X / ACT (P1 - P3): leaves H1, H2 and Z (over ACT).  STEP: the
 // idle waves of P2 form the step's Adam constants and the d mu column scales.
-template <bool STEP>
-__device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, int loss_type, const StepConsts* sc) {
+// PPO (loss_type MLE): P3 also leaves each row's sum_c z^2 as one partial per column tile in PN
+// (and, with `tracks`, that of z_old = (a - mu) / sigma_old in PO), and the step's idle waves
+// of P2 form sum log_std (and sum log_std_old).
+template <bool STEP, bool PPO = false>
+__device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, int loss_type, const StepConsts* sc,
+                                        bool tracks = false) {
   {  // P1
     const Tid q;
     const int wave = q.wave, i = q.i, kq = q.kq;
@@ -246,6 +334,9 @@ __device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, in
     float s = 0.f;
     if (lane < L.A) s = loss_type == LOSS_MLE ? -1.f / ((float)BB * expf(sm[L.ls + lane])) : 2.f / (float)(BB * L.A);
     sm[L.SC + lane] = s;
+  } else if (PPO && STEP && (wave == 10 || (wave == 11 && tracks))) {
+    const float sl = sum_log_std(sm + (wave == 10 ? L.ls : L.LSO), L);
+    if (lane == 0) sm[L.SL + wave - 10] = sl;
   }
   lds_barrier();
   const Tid q3;
@@ -257,10 +348,27 @@ __device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, in
     const float b = sm[L.b3 + c];
     const float sig = loss_type == LOSS_MLE ? expf(sm[L.ls + c]) : 1.f;
     float* pz = sm + L.ACT + (rt * 16 + 4 * kq) * L.AS + c;
+    if constexpr (PPO) {
+      const float sigo = tracks ? expf(sm[L.LSO + c]) : 1.f;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float mu = acc[r] + b, a = pz[r * L.AS];
-      pz[r * L.AS] = c < L.A ? (loss_type == LOSS_MLE ? (a - mu) / sig : mu - a) : 0.f;
+      for (int r = 0; r < 4; ++r) {
+        const float d = pz[r * L.AS] - (acc[r] + b);
+        const float z = c < L.A ? d / sig : 0.f;
+        pz[r * L.AS] = z;
+        const float s = group16_sum(z * z);
+        if (i == 0) sm[L.PN + ct * BB + rt * 16 + 4 * kq + r] = s;
+        if (tracks) {
+          const float zo = c < L.A ? d / sigo : 0.f;
+          const float so = group16_sum(zo * zo);
+          if (i == 0) sm[L.PO + ct * BB + rt * 16 + 4 * kq + r] = so;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mu = acc[r] + b, a = pz[r * L.AS];
+        pz[r * L.AS] = c < L.A ? (loss_type == LOSS_MLE ? (a - mu) / sig : mu - a) : 0.f;
+      }
     }
   }
   lds_barrier();
@@ -311,9 +419,22 @@ struct StepArgs {
   float* step_loss;
 };
 
-__global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
+// PPO's additions to a step (ppo_clip.py:48-55): adv [N] (whitened, fp32) and ll_old [N] are
+// gathered with the rows; ll_old == nullptr is the tracks-mean mode (log_std_old [A] given)
+struct PpoArgs {
+  const float* adv;
+  const float* ll_old;
+  const float* log_std_old;
+  float lo, hi;  // float32(1 - clip_coef), float32(1 + clip_coef): torch.clamp's bounds
+  int32_t* step_clipped;
+};
+
+// The step loop of k_bcfit_steps (PPO = false: `p` unused) and of k_ppo_steps.
+template <bool PPO>
+__device__ __forceinline__ void steps_body(const StepArgs& a, const PpoArgs& p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const Lay L(a.S, a.A);
+  const Lay L(a.S, a.A, PPO);
+  const bool tracks = PPO && p.ll_old == nullptr;
   const Flat F(a.S, a.A);
   const int S = a.S, A = a.A;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i = lane & 15, kq = lane >> 4;
@@ -321,6 +442,7 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
   int* sidx = reinterpret_cast<int*>(sm + L.IDX);
 
   stage_theta(sm, L, F, a.theta);
+  if (PPO && tracks && t < A) sm[L.LSO + t] = p.log_std_old[t];
 
   // ---- ownership: flat offset of each owned parameter (-1: none) and its moments ---------------
   // W1: tiles T = wave + 16 u (jt = T & 1, kt = T >> 1); W3: waves 8-15 (ct = (wave - 8) >> 1,
@@ -369,7 +491,7 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
     if (a.n_steps > 1) sidx[BB + t] = clampi(a.idx[BB + t]);
   }
   __syncthreads();
-  float xr[XU], ar[AU];
+  float xr[XU], ar[AU], advr = 0.f, llor = 0.f;
   // gather map: wave w takes rows 4 w .. 4 w + 3; lane = column within a 64-column group
   auto gather = [&](const int* rows, int lane, int wave) {
 #pragma unroll
@@ -379,6 +501,10 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
     }
 #pragma unroll
     for (int u = 0; u < AU; ++u) ar[u] = lane < A ? a.act[(long long)rows[wave * 4 + u] * a.lda + lane] : 0.f;
+    if (PPO && wave == 15) {  // lane = row
+      advr = p.adv[rows[lane]];
+      if (!tracks) llor = p.ll_old[rows[lane]];
+    }
   };
   auto scatter = [&](int lane, int wave) {
 #pragma unroll
@@ -389,6 +515,10 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
 #pragma unroll
     for (int u = 0; u < AU; ++u)
       if (lane < A) sm[L.ACT + (wave * 4 + u) * L.AS + lane] = ar[u];
+    if (PPO && wave == 15) {
+      sm[L.ADV + lane] = advr;
+      sm[L.LLO + lane] = llor;
+    }
   };
   gather(sidx, lane, wave);
   scatter(lane, wave);
@@ -404,8 +534,27 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
     }
 
     StepConsts sc = {t0 + k + 1, a.lr, a.beta1, a.beta2, a.eps, a.wd};
-    forward<true>(sm, L, a.loss_type, &sc);
+    forward<true, PPO>(sm, L, a.loss_type, &sc, tracks);
     const Adam ad = *reinterpret_cast<const Adam*>(sm + L.ADAM);
+
+    // ---- P3b (PPO): the rows' ratio, surrogate term and weight g = adv LR pass -------------------
+    // pass = 1 inside [lo, hi] (min's two arguments are equal there: its backward halves add up
+    // to the whole, clamp's is inclusive at the bounds); outside only where min takes LR adv
+    if constexpr (PPO) {
+      BCFIT_PHASE_TID();
+      if (wave == 0) {
+        const float lln = row_ll(sm + L.PN, sm[L.SL], L, lane);
+        const float llo = tracks ? row_ll(sm + L.PO, sm[L.SL + 1], L, lane) : sm[L.LLO + lane];
+        const float lr = expf(lln - llo), adv = sm[L.ADV + lane];
+        const bool inside = lr >= p.lo && lr <= p.hi;
+        const bool pass = inside || (lr > p.hi && adv < 0.f) || (lr < p.lo && adv > 0.f);
+        sm[L.G + lane] = pass ? adv * lr : 0.f;
+        sm[L.SURR + lane] = fminf(lr * adv, fminf(fmaxf(lr, p.lo), p.hi) * adv);
+        const unsigned long long out = __ballot(!inside);
+        if (lane == 0) p.step_clipped[k] = __popcll(out);
+      }
+      lds_barrier();
+    }
 
     // ---- P4 -------------------------------------------------------------------------------------
     pf4 g3 = {0.f, 0.f, 0.f, 0.f};
@@ -420,7 +569,8 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
       const float* ps = sm + L.SC + 4 * kq;
       const float* pw = sm + L.W3 + (4 * kq) * HS + jt * 16 + i;
       for (int jj = 0; jj < L.CT; ++jj) {
-        const pf4 z = *reinterpret_cast<const pf4*>(pz + 16 * jj) * *reinterpret_cast<const pf4*>(ps + 16 * jj);
+        pf4 z = *reinterpret_cast<const pf4*>(pz + 16 * jj) * *reinterpret_cast<const pf4*>(ps + 16 * jj);
+        if constexpr (PPO) z *= sm[L.G + rt * 16 + i];
         const float* w = pw + 16 * jj * HS;
         acc = mma(z.x, w[0], acc);
         acc = mma(z.y, w[HS], acc);
@@ -436,18 +586,23 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
       }
     } else {
       if (ct3 < L.CT) {  // gW3[c][j] = sc[c] sum_r Z[r][c] H2[r][j]
-        g3 = tile_tn(sm + L.ACT + ct3 * 16 + i, L.AS, sm + L.H2 + jt3 * 16 + i, HS, kq);
+        g3 = PPO ? tile_tn_w(sm + L.ACT + ct3 * 16 + i, L.AS, sm + L.H2 + jt3 * 16 + i, HS, sm + L.G, kq)
+                 : tile_tn(sm + L.ACT + ct3 * 16 + i, L.AS, sm + L.H2 + jt3 * 16 + i, HS, kq);
 #pragma unroll
         for (int r = 0; r < 4; ++r) g3[r] *= sm[L.SC + ct3 * 16 + 4 * kq + r];
       }
       if (wave == 13 && lane < A) {  // b3
-        const float s = strided_sum(sm + L.ACT + lane, L.AS, BB, [](float x) { return x; });
+        const float s = PPO ? strided_sum2(sm + L.ACT + lane, L.AS, sm + L.G, BB, [](float z, float g) { return z * g; })
+                            : strided_sum(sm + L.ACT + lane, L.AS, BB, [](float x) { return x; });
         adam_lds(sm + L.b3 + lane, ms, vs, s * sm[L.SC + lane], ad);
       } else if (wave == 14 && lane < A && mle) {  // d log_std_c = -(1 / 64) sum_r (z^2 - 1)
-        const float s = strided_sum(sm + L.ACT + lane, L.AS, BB, [](float z) { return z * z - 1.f; });
+        // PPO: -(1 / 64) sum_r g_r (z^2 - 1)
+        const float s = PPO ? strided_sum2(sm + L.ACT + lane, L.AS, sm + L.G, BB,
+                                           [](float z, float g) { return g * (z * z - 1.f); })
+                            : strided_sum(sm + L.ACT + lane, L.AS, BB, [](float z) { return z * z - 1.f; });
         gls = -s * (1.f / BB);  // applied in P5: the loss (wave 15) reads log_std in this phase
       } else if (wave == 15) {  // the step's loss
-        const float tot = amx::wave_sum(row_term(sm, L, a.loss_type, lane));
+        const float tot = amx::wave_sum(PPO ? sm[L.SURR + lane] : row_term(sm, L, a.loss_type, lane));
         if (lane == 0) a.step_loss[k] = mle ? -tot * (1.f / BB) : tot / (float)(BB * A);
       }
     }
@@ -596,6 +751,10 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) {
   if (t == 0) a.adam_step[0] = t0 + a.n_steps;
 }
 
+__global__ __launch_bounds__(NT, 1) void k_bcfit_steps(StepArgs a) { steps_body<false>(a, PpoArgs{}); }
+
+__global__ __launch_bounds__(NT, 1) void k_ppo_steps(StepArgs a, PpoArgs p) { steps_body<true>(a, p); }
+
 struct EvalArgs {
   int S, A, N, loss_type;
   const float* obs;
@@ -606,13 +765,20 @@ struct EvalArgs {
   double* partials;
 };
 
-__global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) {
+// The forward over all rows, 64 at a time: BC's loss (PPO = false: the workgroup's fp64 partial)
+// or every row's LL at theta into ll[N] (PPO = true: the step kernel's row_ll).
+template <bool PPO>
+__device__ __forceinline__ void eval_body(const EvalArgs& a, float* __restrict__ ll) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const Lay L(a.S, a.A);
+  const Lay L(a.S, a.A, PPO);
   const Flat F(a.S, a.A);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   stage_theta(sm, L, F, a.theta);
   __syncthreads();
+  if (PPO && wave == 0) {
+    const float sl = sum_log_std(sm + L.ls, L);
+    if (lane == 0) sm[L.SL] = sl;
+  }
   double bsum = 0.0;
   const int chunks = (a.N + BB - 1) / BB;
   for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
@@ -631,15 +797,23 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) {
       if (lane < a.A) sm[L.ACT + r * L.AS + lane] = a.act[(long long)g * a.lda + lane];
     }
     __syncthreads();
-    forward<false>(sm, L, a.loss_type, nullptr);
+    forward<false, PPO>(sm, L, a.loss_type, nullptr);
     if (wave == 0) {
-      const double v = r0 + lane < a.N ? (double)row_term(sm, L, a.loss_type, lane) : 0.0;
-      bsum += amx::wave_sum(v);
+      if constexpr (PPO) {
+        if (r0 + lane < a.N) ll[r0 + lane] = row_ll(sm + L.PN, sm[L.SL], L, lane);
+      } else {
+        const double v = r0 + lane < a.N ? (double)row_term(sm, L, a.loss_type, lane) : 0.0;
+        bsum += amx::wave_sum(v);
+      }
     }
     __syncthreads();
   }
-  if (t == 0) a.partials[blockIdx.x] = bsum;
+  if (!PPO && t == 0) a.partials[blockIdx.x] = bsum;
 }
+
+__global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) { eval_body<false>(a, nullptr); }
+
+__global__ __launch_bounds__(NT, 1) void k_ppo_old_ll(EvalArgs a, float* ll) { eval_body<true>(a, ll); }
 
 // the workgroups' partials in workgroup order -> mean((mu - a)^2) or -mean(LL)
 __global__ void k_bcfit_eval_sum(const double* __restrict__ partials, int nb, int N, int A, int loss_type,
@@ -727,6 +901,63 @@ extern "C" int amx_bcfit_eval(amx_ctx* ctx, int N, const float* obs, long long l
   hipLaunchKernelGGL(k_bcfit_eval, dim3(nb), dim3(NT), L.bytes(), (hipStream_t)stream, a);
   hipLaunchKernelGGL(k_bcfit_eval_sum, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)work, nb, N, ctx->A,
                      loss_type, loss);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+// ---- PPO (ppo_clip.py:23-121) ------------------------------------------------------------------
+
+extern "C" int amx_ppo_steps(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+                             const float* adv, const float* ll_old, const float* log_std_old, int old_mode,
+                             const int32_t* idx, int n_steps, float* theta, float* adam_m, float* adam_v,
+                             long long* adam_step, double lr, double beta1, double beta2, double eps,
+                             double clip_coef, float* step_loss, int32_t* step_clipped, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_ppo_steps: null ctx");
+  AMX_CHECK_ARG(n_steps >= 0, "amx_ppo_steps: n_steps=%d", n_steps);
+  AMX_CHECK_ARG(idx, "amx_ppo_steps: null idx");
+  int rc = check_data("amx_ppo_steps", ctx, N, obs, ldo, act, lda, LOSS_MLE);
+  if (rc) return rc;
+  AMX_CHECK_ARG(adv, "amx_ppo_steps: null adv");
+  AMX_CHECK_ARG(old_mode == AMX_PPO_OLD_SNAPSHOT || old_mode == AMX_PPO_OLD_TRACKS_MEAN,
+                "amx_ppo_steps: old_mode=%d (0 = snapshot, 1 = tracks mean)", old_mode);
+  AMX_CHECK_ARG(old_mode != AMX_PPO_OLD_SNAPSHOT || ll_old, "amx_ppo_steps: null ll_old in snapshot mode");
+  AMX_CHECK_ARG(old_mode != AMX_PPO_OLD_TRACKS_MEAN || log_std_old,
+                "amx_ppo_steps: null log_std_old in tracks-mean mode");
+  AMX_CHECK_ARG(theta && adam_m && adam_v && adam_step && step_loss && step_clipped,
+                "amx_ppo_steps: null theta / adam_m / adam_v / adam_step / step_loss / step_clipped");
+  AMX_CHECK_ARG(((uintptr_t)adam_step & 7u) == 0, "amx_ppo_steps: misaligned adam_step");
+  AMX_CHECK_ARG(lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+                "amx_ppo_steps: lr=%g betas=(%g, %g) eps=%g", lr, beta1, beta2, eps);
+  AMX_CHECK_ARG(clip_coef >= 0.0 && clip_coef < 1.0, "amx_ppo_steps: clip_coef=%g (0 <= c < 1)", clip_coef);
+  if (n_steps == 0) return AMX_OK;
+  const Lay L(ctx->S, ctx->A, true);
+  AMX_CHECK_ARG(L.bytes() <= 160 * 1024, "amx_ppo_steps: %zu B of LDS", L.bytes());
+  rc = allow_lds(k_ppo_steps, L.bytes());
+  if (rc) return rc;
+  StepArgs a = {ctx->S, ctx->A, N, n_steps, LOSS_MLE, obs, ldo, act, lda, idx, theta, adam_m, adam_v, adam_step,
+                lr, beta1, beta2, eps, 0.0, step_loss};
+  PpoArgs p = {adv, old_mode == AMX_PPO_OLD_SNAPSHOT ? ll_old : nullptr, log_std_old, (float)(1.0 - clip_coef),
+               (float)(1.0 + clip_coef), step_clipped};
+  hipLaunchKernelGGL(k_ppo_steps, dim3(1), dim3(NT), L.bytes(), (hipStream_t)stream, a, p);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+extern "C" int amx_ppo_old_ll(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+                              const float* theta, float* ll_old, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_ppo_old_ll: null ctx");
+  int rc = check_data("amx_ppo_old_ll", ctx, N, obs, ldo, act, lda, LOSS_MLE);
+  if (rc) return rc;
+  AMX_CHECK_ARG(theta && ll_old, "amx_ppo_old_ll: null theta / ll_old");
+  const Lay L(ctx->S, ctx->A, true);
+  AMX_CHECK_ARG(L.bytes() <= 160 * 1024, "amx_ppo_old_ll: %zu B of LDS", L.bytes());
+  rc = allow_lds(k_ppo_old_ll, L.bytes());
+  if (rc) return rc;
+  const int chunks = (N + BB - 1) / BB;
+  int nb = ctx->n_cus > 0 ? ctx->n_cus : 1;
+  if (nb > chunks) nb = chunks;
+  EvalArgs a = {ctx->S, ctx->A, N, LOSS_MLE, obs, ldo, act, lda, theta, nullptr};
+  hipLaunchKernelGGL(k_ppo_old_ll, dim3(nb), dim3(NT), L.bytes(), (hipStream_t)stream, a, ll_old);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
 }

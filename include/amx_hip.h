@@ -847,6 +847,41 @@ int amx_bcfit_eval(amx_ctx* ctx, int N, const float* obs, long long ldo, const f
                    long long lda, const float* theta, int loss_type, void* work, double* loss,
                    void* stream);
 
+/* ---- the PPO policy update (PPO.train_from_paths) ------------------------------ */
+
+enum { AMX_PPO_OLD_SNAPSHOT = 0, AMX_PPO_OLD_TRACKS_MEAN = 1 };
+
+/* n_steps consecutive mini-batch steps of PPO.train_from_paths' loop
+ * (mjrl/mjrl/algos/ppo_clip.py:88-97) in one launch of one workgroup, by the design and with the
+ * shapes, theta / adam_m / adam_v / adam_step and idx of amx_bcfit_steps (its step body: the
+ * AMX_BC_MLE forward, backward and Adam).  Step k also gathers adv[idx] (fp32 [N], already
+ * whitened) and forms per row
+ *   LL_new = (-0.5 sum_c z^2 - sum log_std) - 0.5 A log(2 pi),  z = (a - mu) / exp(log_std),
+ *   LL_old: AMX_PPO_OLD_SNAPSHOT     ll_old[idx] (fp32 [N], amx_ppo_old_ll at the old theta);
+ *           AMX_PPO_OLD_TRACKS_MEAN  the same sum from the step's own mu with log_std_old [A]
+ *                                    (the old mean network shares the new one's storage),
+ *   LR = exp(LL_new - LL_old),  lo / hi = float32(1 -/+ clip_coef),
+ *   loss = -mean(min(LR adv, clamp(LR, lo, hi) adv))              (ppo_clip.py:48-55),
+ * and autograd's gradient: d loss / d LL_new = -(1 / 64) g, g = adv LR pass, pass = 1 for
+ * lo <= LR <= hi (min's two arguments are equal there and its halves add up; clamp passes at
+ * its bounds), for LR > hi only where adv < 0 and for LR < lo only where adv > 0.  The
+ * gradient flows through LL_new only.  All seven tensors take the Adam step (no weight decay);
+ * log_std is not clamped.  step_loss[k] = the loss, step_clipped[k] = rows with LR outside
+ * [lo, hi] (device, n_steps each).  The sum over c runs in one fixed order in both LLs and in
+ * amx_ppo_old_ll, so equal policies give LR == 1 exactly; cutting a run of steps into several
+ * calls changes no bit. */
+int amx_ppo_steps(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act,
+                  long long lda, const float* adv, const float* ll_old, const float* log_std_old,
+                  int old_mode, const int32_t* idx, int n_steps, float* theta, float* adam_m,
+                  float* adam_v, long long* adam_step, double lr, double beta1, double beta2,
+                  double eps, double clip_coef, float* step_loss, int32_t* step_clipped,
+                  void* stream);
+
+/* ll_old[r] = LL of row r at theta for all N rows (device, fp32): the step kernel's forward and
+ * row arithmetic, 64 rows at a time on one workgroup per compute unit.  One launch. */
+int amx_ppo_old_ll(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act,
+                   long long lda, const float* theta, float* ll_old, void* stream);
+
 /* ---- RNG ----------------------------------------------------------------------- */
 
 /* Philox4x32-10 block for (key = seed, counter = {ctr0, ctr1, ctr2, ctr3}), written
