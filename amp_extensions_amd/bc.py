@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .optstate import pack_state, policy_layout, read_state, write_state
 
 BATCH = 64
 HIDDEN = (32, 32)
@@ -60,7 +61,9 @@ class DeviceBC:
         self.loss_type = loss_type
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), \
             float(weight_decay)
-        self.P = int(ctx.lib.amx_npg_param_count(self.S, self.A))
+        self.layout = policy_layout(self.S, self.A, HIDDEN)
+        self.P = self.layout.size
+        assert self.P == ctx.lib.amx_npg_param_count(self.S, self.A)
         if ctx.lib.amx_bcfit_work(self.S, self.A) < 0:
             raise NotImplementedError(ctx.lib.amx_last_error().decode())
         self.theta = torch.zeros(self.P, dtype=torch.float32, device=ctx.device)
@@ -78,10 +81,6 @@ class DeviceBC:
 
     # ---- Adam state (DeviceMLPBaseline's surface) -----------------------------------------------
 
-    def _param_shapes(self):
-        S, A, (h0, h1) = self.S, self.A, HIDDEN
-        return [(h0, S), (h0,), (h1, h0), (h1,), (A, h1), (A,), (A,)]
-
     def _trained(self) -> int:
         """Parameters the loss trains: log_std has no gradient under MSE."""
         return 7 if self.loss_type == "MLE" else 6
@@ -98,22 +97,9 @@ class DeviceBC:
         """Adam state of a torch.optim.Adam over the policy's trainable_params (W1, b1, W2, b2,
         W3, b3, log_std) -> the device moments and step count.  Parameters without state load as
         zeros.  The device keeps one step count, so the trained parameters must agree on it."""
-        params = optimizer.param_groups[0]["params"]
-        shapes = self._param_shapes()
-        if len(params) != len(shapes):
-            raise ValueError(f"optimizer holds {len(params)} parameters, the policy has {len(shapes)}")
-        m, v, steps, o = torch.zeros(self.P), torch.zeros(self.P), set(), 0
-        for k, (p, shape) in enumerate(zip(params, shapes)):
-            n = int(np.prod(shape))
-            st = optimizer.state.get(p, {})
-            if st:
-                if tuple(st["exp_avg"].shape) != shape:
-                    raise ValueError(f"optimizer state of shape {tuple(st['exp_avg'].shape)}, expected {shape}")
-                m[o:o + n] = st["exp_avg"].detach().float().cpu().reshape(-1)
-                v[o:o + n] = st["exp_avg_sq"].detach().float().cpu().reshape(-1)
-            if k < self._trained():
-                steps.add(int(st["step"]) if st else 0)
-            o += n
+        kind, _, states = read_state(optimizer, kinds=("adam",))
+        m, v = pack_state(self.layout, kind, states)
+        steps = {step for step, _, _ in states[:self._trained()]}
         if len(steps) != 1:
             raise NotImplementedError(f"the trained parameters are at different Adam steps {sorted(steps)}")
         dm, dv, dstep = self._adam_state()
@@ -125,16 +111,7 @@ class DeviceBC:
         """(step, [exp_avg per parameter], [exp_avg_sq per parameter]) on the host, in torch's
         parameter order and shapes (log_std's entries stay as loaded under MSE)."""
         dm, dv, dstep = self._adam_state()
-        m, v = dm.cpu(), dv.cpu()
-
-        def cut(x):
-            out, o = [], 0
-            for shape in self._param_shapes():
-                n = int(np.prod(shape))
-                out.append(x[o:o + n].view(shape).clone())
-                o += n
-            return out
-        return int(dstep.item()), cut(m), cut(v)
+        return int(dstep.item()), self.layout.unpack(dm.cpu()), self.layout.unpack(dv.cpu())
 
     # ---- the fit ----------------------------------------------------------------------------------
 
@@ -219,14 +196,8 @@ class DataLog:
 
 
 def check_adam(optimizer) -> None:
-    """The optimizers the device fits implement: torch.optim.Adam, one group, no amsgrad / maximize."""
-    if type(optimizer) is not torch.optim.Adam:
-        raise NotImplementedError(f"the device fit implements torch.optim.Adam, not {type(optimizer).__name__}")
-    if len(optimizer.param_groups) != 1:
-        raise NotImplementedError("the device fit supports one parameter group")
-    g = optimizer.param_groups[0]
-    if g.get("amsgrad", False) or g.get("maximize", False):
-        raise NotImplementedError("the device fit implements Adam without amsgrad / maximize")
+    """The optimizers the policy fits implement: torch.optim.Adam, one group, no amsgrad / maximize."""
+    read_state(optimizer, kinds=("adam",))
 
 
 def write_optimizer(optimizer, d) -> None:
@@ -234,12 +205,8 @@ def write_optimizer(optimizer, d) -> None:
     exp_avg_sq per trained parameter), so a later fit, here or on the host, resumes where this
     one stopped."""
     step, ms, vs = d.adam_state()
-    if step == 0:
-        return
-    params = optimizer.param_groups[0]["params"]
-    for p, m, v in list(zip(params, ms, vs))[:d._trained()]:
-        optimizer.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.to(p.device).view_as(p),
-                              "exp_avg_sq": v.to(p.device).view_as(p)}
+    if step:
+        write_state(optimizer, "adam", step, ms[:d._trained()], vs[:d._trained()])
 
 
 class BC:

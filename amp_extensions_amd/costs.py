@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import _native as N
 from .engine import AmxContext, RffMap, round_up, split_bf16x3, split_f16x2
+from .optstate import common_step, disc_layout, pack_state, read_state, write_state
 
 
 def device_discrepancy(ensemble, states, actions) -> torch.Tensor:
@@ -407,18 +408,17 @@ class GAILCost:
         if isinstance(weights, dict):
             n = len(weights) // 2
             weights = [(weights[f"net.{2 * i}.weight"], weights[f"net.{2 * i}.bias"]) for i in range(n)]
-        opt = None if optimizer is None else self._parse_optimizer(optimizer, weights)
-        dev = self.ctx.device
+        widths = [int(W.shape[0]) for W, _ in weights[:-1]]
         self.Kin = round_up(self.input_dim, 32)
+        layout = disc_layout(self.input_dim, self.Kin, widths, [round_up(h, 128) for h in widths])
+        opt = None if optimizer is None else self._parse_optimizer(optimizer, layout)
+        *hidden, w3, b3 = layout.views(layout.pack([t for Wb in weights for t in Wb]))
+        dev = self.ctx.device
+        self.layout = layout
         self.dev_layers = []
-        k_in, k_pad = self.input_dim, self.Kin
-        for (W, b) in weights[:-1]:
-            out = W.shape[0]
-            out_p = round_up(out, 128)
-            Wp = torch.zeros(out_p, k_pad, dtype=torch.float32)
-            Wp[:out, :k_in] = W.float().cpu()
-            bp = torch.zeros(out_p, dtype=torch.float32)
-            bp[:out] = b.float().cpu()
+        k_pad = self.Kin
+        for Wp, bp in zip(hidden[0::2], hidden[1::2]):
+            out_p = Wp.shape[0]
             Wd = Wp.to(dev).contiguous()
             W3 = None
             if self.gemm == "bf16x6":
@@ -427,25 +427,20 @@ class GAILCost:
                 W2, wexp = split_f16x2(self.ctx, Wd.unsqueeze(0))
                 W3 = (W2[0], wexp[0])
             self.dev_layers.append((Wd, bp.to(dev).contiguous(), out_p, k_pad, W3))
-            k_in, k_pad = out, out_p
-        W3, b3 = weights[-1]
-        w3 = torch.zeros(k_pad, dtype=torch.float32)
-        w3[:k_in] = W3.float().cpu().view(-1)
-        self.w3 = w3.to(dev).contiguous()
-        self.b3 = float(b3.float().cpu().view(-1)[0])
+            k_pad = out_p
+        self.w3 = w3.reshape(-1).to(dev).contiguous()
+        self.b3 = float(b3[0])
         self.h_last = k_pad
         self._ws = {}
         self._train, self._steps, self._disc_opt = None, 0, None
         self._dev_newer = True   # the host mirror follows the uploaded weights
         if opt is not None:
-            self._opt_kind, self._opt_lr, self._opt_p1, self._steps, state = opt
+            self._opt_kind, self._opt_lr, self._opt_p1, self._steps, s1, s2 = opt
             t = self._train_state()
             t.step.fill_(self._steps)
-            for vec, rows in zip((t.s1, t.s2), state):
-                if vec is not None and rows is not None:
-                    for (off, shape, valid), v in zip(self._param_slices(), rows):
-                        vec[off:off + shape[0] * shape[1]].view(shape)[:valid[0], :valid[1]] = \
-                            v.detach().float().reshape(valid).to(dev)
+            t.s1.copy_(s1)
+            if s2 is not None:
+                t.s2.copy_(s2)
 
     # ---- training: update_disc / compute_chi2_distance (gail_cost.py:94-228) ----------------
 
@@ -457,48 +452,24 @@ class GAILCost:
             raise NotImplementedError(f"update_disc on the device supports {self._SUPPORTED}; this discriminator "
                                       f"has {len(self._layers) - 1} hidden layer(s)")
 
-    def _parse_optimizer(self, sd, weights):
-        """(kind, lr, p1, steps, (state1 rows, state2 rows)) of a torch optimizer state_dict over
-        the six tensors; refuses what amx_dfit_step does not cover, before anything is allocated."""
-        if len(weights) != 3:
+    def _parse_optimizer(self, sd, layout):
+        """(kind, lr, p1, steps, state1, state2) of a torch optimizer state_dict over the six tensors,
+        the state in `layout`'s host vectors; refuses what amx_dfit_step does not cover, before
+        anything is allocated."""
+        if len(layout.live) != 6:
             raise NotImplementedError(f"update_disc on the device supports {self._SUPPORTED}; the weights given "
-                                      f"have {len(weights) - 1} hidden layer(s)")
-        groups = sd["param_groups"]
-        g = groups[0]
-        if len(groups) != 1 or len(g["params"]) != 6:
-            raise NotImplementedError(f"one parameter group over the six tensors is supported ({self._SUPPORTED})")
-        if "momentum" in g:
-            if g.get("nesterov") or g.get("dampening", 0) != 0 or g.get("weight_decay", 0) != 0 or g.get("maximize"):
+                                      f"have {len(layout.live) // 2 - 1} hidden layer(s)")
+        kind, g, states = read_state(sd)
+        if kind == "sgd":
+            if g.get("nesterov") or g.get("weight_decay", 0) != 0:
                 raise NotImplementedError(f"unsupported SGD options; supported: {self._SUPPORTED}")
-            kind, p1 = "sgd", float(g["momentum"])
+            p1 = float(g["momentum"])
+            steps = int(any(s1 is not None for _, s1, _ in states))   # SGD keeps no count
         else:
-            if tuple(g["betas"]) != (0.9, 0.999) or g.get("weight_decay", 0) != 0 or g.get("amsgrad") or \
-                    g.get("maximize"):
+            if tuple(g["betas"]) != (0.9, 0.999) or g.get("weight_decay", 0) != 0:
                 raise NotImplementedError(f"unsupported Adam options; supported: {self._SUPPORTED}")
-            kind, p1 = "adam", float(g["eps"])
-        st = [sd["state"].get(p) for p in g["params"]]
-        steps, s1, s2 = 0, None, None
-        if all(s for s in st):
-            if kind == "sgd":
-                if all(s.get("momentum_buffer") is not None for s in st):
-                    s1, steps = [s["momentum_buffer"] for s in st], 1   # SGD keeps no count
-            else:
-                s1, s2 = [s["exp_avg"] for s in st], [s["exp_avg_sq"] for s in st]
-                steps = int(float(st[0]["step"]))
-        return kind, float(g["lr"]), p1, steps, (s1, s2)
-
-    def _param_slices(self):
-        """(offset, padded [rows, cols], valid [rows, cols]) of W0, b0, W1, b1, w2, b2 in the flat
-        optimizer-state vectors (amx_dfit_param_count's layout)."""
-        (_, _, H0p, Dp, _), (_, _, H1p, _, _) = self.dev_layers
-        h0, h1 = self._layers[0].out_features, self._layers[1].out_features
-        shapes = [((H0p, Dp), (h0, self.input_dim)), ((1, H0p), (1, h0)), ((H1p, H0p), (h1, h0)), ((1, H1p), (1, h1)),
-                  ((1, H1p), (1, h1)), ((1, 4), (1, 1))]
-        out, off = [], 0
-        for shape, valid in shapes:
-            out.append((off, shape, valid))
-            off += shape[0] * shape[1]
-        return out
+            p1, steps = float(g["eps"]), common_step(states)
+        return (kind, float(g["lr"]), p1, steps) + pack_state(layout, kind, states)
 
     def _train_state(self):
         """Device optimizer state beside the master weights (allocated once)."""
@@ -511,6 +482,7 @@ class GAILCost:
         P = c.lib.amx_dfit_param_count(Dp, H0p, H1p)
         if P < 0:
             raise N.AmxNativeError("amx_dfit_param_count: " + c.lib.amx_last_error().decode())
+        assert P == self.layout.size
         t = SimpleNamespace(P=P, work={}, idx={})
         t.s1 = torch.zeros(P, dtype=torch.float32, device=dev)
         t.s2 = torch.zeros(P, dtype=torch.float32, device=dev) if self._opt_kind == "adam" else None
@@ -661,26 +633,16 @@ class GAILCost:
             self._disc_opt = self._make_opt()
         if not self._dev_newer:
             return
+        padded = [t for Wd, bp, _, _, _ in self.dev_layers for t in (Wd, bp)] + [self.w3]
+        flat = torch.cat([t.reshape(-1).cpu() for t in padded] + [torch.tensor([self.b3, 0.0, 0.0, 0.0])])
         with torch.no_grad():
-            k_in = self.input_dim
-            for lin, (Wd, bp, _, _, _) in zip(self._layers[:-1], self.dev_layers):
-                lin.weight.copy_(Wd[:lin.out_features, :k_in].cpu())
-                lin.bias.copy_(bp[:lin.out_features].cpu())
-                k_in = lin.out_features
-            self._layers[-1].weight.copy_(self.w3[:k_in].view(1, -1).cpu())
-            self._layers[-1].bias.fill_(self.b3)
+            for p, live in zip(self._disc.parameters(), self.layout.unpack(flat)):
+                p.copy_(live)
         self._disc_opt = self._make_opt()
         t = self._train
         if t is not None and self._steps > 0:
-            s1, s2 = t.s1.cpu(), (None if t.s2 is None else t.s2.cpu())
-            for p, (off, shape, valid) in zip(self._disc.parameters(), self._param_slices()):
-                def cut(v, off=off, shape=shape, valid=valid, p=p):
-                    return v[off:off + shape[0] * shape[1]].view(shape)[:valid[0], :valid[1]].reshape(p.shape).clone()
-                if self._opt_kind == "sgd":
-                    self._disc_opt.state[p] = {"momentum_buffer": cut(s1)}
-                else:
-                    self._disc_opt.state[p] = {"step": torch.tensor(float(self._steps)), "exp_avg": cut(s1),
-                                               "exp_avg_sq": cut(s2)}
+            write_state(self._disc_opt, self._opt_kind, self._steps, self.layout.unpack(t.s1.cpu()),
+                        None if t.s2 is None else self.layout.unpack(t.s2.cpu()))
         self._dev_newer = False
 
     @property

@@ -18,6 +18,7 @@ import torch
 
 from . import _native as N
 from .humanoid import TerminationConfig
+from .optstate import ensemble_layout, pack_state
 
 
 def round_up(x: int, m: int) -> int:
@@ -138,6 +139,11 @@ def split_f16x2(ctx: AmxContext, W: torch.Tensor, out=None):
     return W2, wexp
 
 
+def flat_pairs(pairs, L: int):
+    """[(W, b), ...] of L + 1 layers -> [W0, b0, W1, ...] (torch's parameter order); None: no tensors."""
+    return [t for Wb in pairs or [(None, None)] * (L + 1) for t in Wb]
+
+
 def _check_dev(t: torch.Tensor, dtype, name: str, device) -> None:
     if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous {dtype} tensor on {device}, got "
@@ -172,6 +178,7 @@ class DeviceEnsemble:
         self.hidden = hidden
         if round_up(hidden, 128) != Hp or len(weights[0]) != L + 1:
             raise ValueError("weights do not match the context's (hidden, n_hidden)")
+        self.layout = ensemble_layout(ctx.S, ctx.A, hidden, L, ctx.k0_pad, Hp, ctx.ldk, ctx.n_out_pad)  # per member
         self.W = self.b = self.W3 = self.W2 = self.wexp = None
         self.set_weights(weights)
         ctx.set_normalizers(norms)
@@ -189,34 +196,19 @@ class DeviceEnsemble:
         buffers are updated in place, so engines and captured graphs that hold their pointers
         see the new weights (DynamicsEnsemble.load_ensemble, dynamics.py:118-131)."""
         ctx = self.ctx
-        S, A, M, Hp, L = ctx.S, ctx.A, ctx.M, ctx.Hp, ctx.L
+        M, L, dev = ctx.M, ctx.L, ctx.device
         if len(weights) != M:
             raise ValueError(f"expected {M} ensemble members, got {len(weights)}")
-        hidden = self.hidden
-        dev, k0 = ctx.device, ctx.k0_pad
-        # original input column -> padded activation column
-        colmap = np.concatenate([np.arange(S + A)] + [k0 + i * Hp + np.arange(hidden) for i in range(L)])
-        Ws, bs = [], []
-        for i in range(L + 1):
-            last = i == L
-            n_rows = ctx.n_out_pad if last else Hp
-            Kp = ctx.ldk if last else k0 + i * Hp
-            Wp = torch.zeros(M, n_rows, Kp, dtype=torch.float32)
-            bp = torch.zeros(M, n_rows, dtype=torch.float32)
-            for m in range(M):
-                if len(weights[m]) != L + 1:
-                    raise ValueError(f"member {m}: {len(weights[m])} layers, expected {L + 1}")
-                W_m, b_m = weights[m][i]
-                W_m = torch.as_tensor(W_m).detach().float().cpu()
-                out_dim, in_dim = W_m.shape
-                exp_in = S + A + i * hidden
-                if in_dim != exp_in or out_dim != (S if last else hidden):
-                    raise ValueError(f"layer {i} of member {m}: shape {tuple(W_m.shape)}, expected "
-                                     f"({S if last else hidden}, {exp_in})")
-                Wp[m, :out_dim][:, torch.from_numpy(colmap[:in_dim])] = W_m
-                bp[m, :out_dim] = torch.as_tensor(b_m).detach().float().cpu()
-            Ws.append(Wp)
-            bs.append(bp)
+        rows = []
+        for m, w in enumerate(weights):
+            if len(w) != L + 1:
+                raise ValueError(f"member {m}: {len(w)} layers, expected {L + 1}")
+            try:
+                rows.append(self.layout.pack([t for Wb in w for t in Wb]))
+            except ValueError as e:
+                raise ValueError(f"member {m}: {e}") from None
+        padded = self.layout.views(torch.stack(rows))
+        Ws, bs = padded[0::2], padded[1::2]
         if self.W is None:
             self.W = [w.to(dev).contiguous() for w in Ws]
             self.b = [b.to(dev).contiguous() for b in bs]
@@ -471,28 +463,6 @@ class DeviceEnsemble:
     # ---- training (DynamicsModel.train_step / validate_step, dynamics.py:236-261) ------------
     _fit = None  # training state, allocated by fit_begin
 
-    def _colmap(self) -> np.ndarray:
-        """nn.Linear input column -> padded dense-concat column."""
-        c = self.ctx
-        return np.concatenate([np.arange(c.S + c.A)] + [c.k0_pad + i * c.Hp + np.arange(self.hidden)
-                                                         for i in range(c.L)])
-
-    def _layer_dims(self, i: int):
-        """(padded rows, padded K, rows, in) of layer i."""
-        c = self.ctx
-        last = i == c.L
-        return (c.n_out_pad if last else c.Hp, c.ldk if last else c.k0_pad + i * c.Hp,
-                c.S if last else self.hidden, c.S + c.A + i * self.hidden)
-
-    def _flat_views(self, flat: torch.Tensor):
-        """[(W view [M][N_i][K_i], b view [M][N_i])] of a flat [M][param_count] training vector."""
-        out, o = [], 0
-        for i in range(self.ctx.L + 1):
-            N_, K_, _, _ = self._layer_dims(i)
-            out.append((flat[:, o:o + N_ * K_].view(-1, N_, K_), flat[:, o + N_ * K_:o + N_ * K_ + N_]))
-            o += N_ * K_ + N_
-        return out
-
     def fit_begin(self, train_data, optim: str, lr: float, p1: float, batch_size: int, val_data=None,
                   opt_state=None, num_models: int | None = None, hidden_sizes=None) -> None:
         """Allocate the training state (gradients, optimizer state in the padded layout, the step
@@ -524,11 +494,19 @@ class DeviceEnsemble:
                 raise ValueError(f"{name} data: shapes {tuple(s.shape)}, {tuple(a.shape)}, {tuple(s2.shape)} do not "
                                  f"match S={c.S}, A={c.A}")
             data[name] = (s, a, s2)
+        host = None
+        if opt_state is not None:
+            if len(opt_state) != c.M:
+                raise ValueError(f"optimizer state of {len(opt_state)} members, expected {c.M}")
+            host = [pack_state(self.layout, optim, [(0, a, b) for a, b in zip(flat_pairs(st.get("s1"), c.L),
+                                                                               flat_pairs(st.get("s2"), c.L))])
+                    for st in opt_state]
         P = int(c.lib.amx_efit_param_count(c.h))
         Bt = round_up(int(batch_size), 128)
         floats = int(c.lib.amx_efit_work_floats(c.h, Bt))
         if P <= 0 or floats <= 0:
             raise N.AmxNativeError("amx_efit sizes: " + c.lib.amx_last_error().decode())
+        assert P == self.layout.size
         dev = c.device
         f = dict(optim=optim, lr=float(lr), p1=float(p1), batch_size=int(batch_size), Bt=Bt, P=P)
         f["data"] = {k: tuple(x.detach().to(dev, torch.float32).contiguous() for x in v) for k, v in data.items()}
@@ -539,24 +517,11 @@ class DeviceEnsemble:
         f["work"] = torch.zeros(floats, dtype=torch.float32, device=dev)
         f["Wp"] = (N.C.c_void_p * (c.L + 1))(*[w.data_ptr() for w in self.W])
         f["bp"] = (N.C.c_void_p * (c.L + 1))(*[b.data_ptr() for b in self.b])
-        if opt_state is not None:
-            if len(opt_state) != c.M:
-                raise ValueError(f"optimizer state of {len(opt_state)} members, expected {c.M}")
+        if host is not None:
             f["step"].copy_(torch.tensor([int(st["step"]) for st in opt_state], dtype=torch.int64))
-            cm = torch.from_numpy(self._colmap())
-            for key in ("s1", "s2"):
-                if f[key] is None:
-                    continue
-                host = torch.zeros(c.M, P, dtype=torch.float32)
-                for i, (Wv, bv) in enumerate(self._flat_views(host)):
-                    _, _, rows, n_in = self._layer_dims(i)
-                    for m, st in enumerate(opt_state):
-                        if st.get(key) is None:
-                            continue
-                        Wm, bm = st[key][i]
-                        Wv[m, :rows][:, cm[:n_in]] = torch.as_tensor(Wm).detach().float().cpu()
-                        bv[m, :rows] = torch.as_tensor(bm).detach().float().cpu()
-                f[key].copy_(host)
+            f["s1"].copy_(torch.stack([s1 for s1, _ in host]))
+            if f["s2"] is not None:
+                f["s2"].copy_(torch.stack([s2 for _, s2 in host]))
         self._fit = f
 
     def fit_epoch(self, idx, sizes, train: bool = True, grad_clip: float = 0.0, split: str = "train") -> np.ndarray:
@@ -592,23 +557,18 @@ class DeviceEnsemble:
         """The device training state in nn.Linear layout: (weights, opt_state) with weights[m] =
         [(W, b), ...] and opt_state[m] = {'step', 's1', 's2'} as fit_begin takes them."""
         f, c = self._fit, self.ctx
-        cm = torch.from_numpy(self._colmap())
-        Wh, bh = [w.cpu() for w in self.W], [b.cpu() for b in self.b]
+        padded = [t.cpu().reshape(c.M, -1) for Wb in zip(self.W, self.b) for t in Wb]
+        host = {"W": torch.cat(padded, 1), "s1": f["s1"].cpu(), "s2": None if f["s2"] is None else f["s2"].cpu()}
         steps = f["step"].cpu().tolist()
-        views = {k: (self._flat_views(f[k].cpu()) if f[k] is not None else None) for k in ("s1", "s2")}
 
-        def unpad(Wv, bv, i, m):
-            _, _, rows, n_in = self._layer_dims(i)
-            return Wv[m, :rows][:, cm[:n_in]].clone(), bv[m, :rows].clone()
+        def live(key, m):  # [(W, b), ...] of member m in nn.Linear layout
+            if host[key] is None:
+                return None
+            t = self.layout.unpack(host[key][m])
+            return list(zip(t[0::2], t[1::2]))
 
-        weights, opt = [], []
-        for m in range(c.M):
-            weights.append([unpad(Wh[i], bh[i], i, m) for i in range(c.L + 1)])
-            st = {"step": int(steps[m])}
-            for k, v in views.items():
-                st[k] = None if v is None else [unpad(v[i][0], v[i][1], i, m) for i in range(c.L + 1)]
-            opt.append(st)
-        return weights, opt
+        weights = [live("W", m) for m in range(c.M)]
+        return weights, [{"step": int(steps[m]), "s1": live("s1", m), "s2": live("s2", m)} for m in range(c.M)]
 
     def fit_refresh(self) -> None:
         """Re-split the inference limb images from the trained master weights, in place: engines

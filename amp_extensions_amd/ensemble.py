@@ -41,7 +41,8 @@ import torch
 import torch.nn as nn
 from torch.utils.data import DataLoader, Dataset
 
-from .engine import AmxContext, DeviceEnsemble
+from .engine import AmxContext, DeviceEnsemble, flat_pairs
+from .optstate import common_step, read_state, write_state
 
 # DynamicsEnsemble's default optimizer arguments (dynamics.py:32)
 DEFAULT_OPTIM_ARGS = {'optim': 'sgd', 'lr': 1e-4, 'momentum': 0.9}
@@ -265,46 +266,29 @@ class DynamicsEnsemble:
         included); anything the device step does not implement raises."""
         cfg = None
         for m in self.models:
-            opt = m.optimizer
-            if len(opt.param_groups) != 1:
-                raise NotImplementedError("one param_group per member")
-            pg = opt.param_groups[0]
-            if isinstance(opt, torch.optim.Adam):
-                if (tuple(pg["betas"]) != (0.9, 0.999) or pg["weight_decay"] != 0 or pg["amsgrad"]
-                        or pg.get("maximize")):
+            kind, pg, _ = read_state(m.optimizer)
+            if kind == "adam":
+                if tuple(pg["betas"]) != (0.9, 0.999) or pg["weight_decay"] != 0:
                     raise NotImplementedError(f"Adam options {pg['betas']}, weight_decay={pg['weight_decay']}, "
                                               f"amsgrad={pg['amsgrad']} (supported: torch's defaults with lr, eps)")
                 c = ("adam", float(pg["lr"]), float(pg["eps"]))
-            elif isinstance(opt, torch.optim.SGD):
-                if not pg["nesterov"] or pg["dampening"] != 0 or pg["weight_decay"] != 0 or pg.get("maximize"):
+            else:
+                if not pg["nesterov"] or pg["weight_decay"] != 0:
                     raise NotImplementedError("SGD options (supported: momentum with nesterov=True, dampening 0)")
                 c = ("sgd", float(pg["lr"]), float(pg["momentum"]))
-            else:
-                raise NotImplementedError(f"optimizer {type(opt).__name__}")
             if cfg is not None and c != cfg:
                 raise NotImplementedError("members with different optimizer settings")
             cfg = c
         return cfg
 
-    def _host_opt_state(self, optim):
-        """The members' optimizer state in DeviceEnsemble.fit_begin's form (None when fresh)."""
-        out, any_state = [], False
+    def _host_opt_state(self):
+        """The members' optimizer state in DeviceEnsemble.fit_begin's form."""
+        out = []
         for m in self.models:
-            st = {"step": 0, "s1": None, "s2": None}
-            params = list(m.model.parameters())
-            states = [m.optimizer.state.get(p, {}) for p in params]
-            k1, k2 = ("exp_avg", "exp_avg_sq") if optim == "adam" else ("momentum_buffer", None)
-            if all(s_.get(k1) is not None for s_ in states):
-                any_state = True
-                st["s1"] = [(states[2 * i][k1], states[2 * i + 1][k1]) for i in range(len(params) // 2)]
-                if k2:
-                    st["s2"] = [(states[2 * i][k2], states[2 * i + 1][k2]) for i in range(len(params) // 2)]
-                    steps = {int(float(s_["step"])) for s_ in states}
-                    if len(steps) != 1:
-                        raise NotImplementedError("parameters of one member at different Adam steps")
-                    st["step"] = steps.pop()
-            out.append(st)
-        return out if any_state else None
+            _, _, states = read_state(m.optimizer)
+            pairs = lambda j: [(states[i][j], states[i + 1][j]) for i in range(0, len(states), 2)]  # noqa: E731
+            out.append({"step": common_step(states), "s1": pairs(1), "s2": pairs(2)})
+        return out
 
     def sync_to_host(self):
         """Copy the device master weights and optimizer state into `models[k].model` and
@@ -315,18 +299,12 @@ class DynamicsEnsemble:
         weights, opt = self.engine.fit_state()
         with torch.no_grad():
             for m, w, st in zip(self.models, weights, opt):
-                params = list(m.model.parameters())
                 for i, lin in enumerate(m.model.fc_layers):
                     lin.weight.copy_(w[i][0]), lin.bias.copy_(w[i][1])
                 if not self._fit_stepped and st["step"] == 0:
                     continue
-                for j, p in enumerate(params):
-                    i, k = divmod(j, 2)
-                    if optim == "adam":
-                        m.optimizer.state[p] = {"step": torch.tensor(float(st["step"]), dtype=torch.float32),
-                                                "exp_avg": st["s1"][i][k], "exp_avg_sq": st["s2"][i][k]}
-                    else:
-                        m.optimizer.state[p] = {"momentum_buffer": st["s1"][i][k]}
+                L = len(w) - 1
+                write_state(m.optimizer, optim, st["step"], flat_pairs(st["s1"], L), flat_pairs(st["s2"], L))
 
     def train_on_device(self, epochs, validate=False, logger=None, log_epoch=False, grad_clip=0, save_path=None,
                         save_checkpoints=False, writer=None):
@@ -354,7 +332,7 @@ class DynamicsEnsemble:
         va = _dataset_tensors(self.validate_dataset) if validate else None
         M, bs = self.num_models, int(self.batch_size)
         eng = self.engine
-        eng.fit_begin(tr, optim, lr, p1, bs, val_data=va, opt_state=self._host_opt_state(optim), num_models=M,
+        eng.fit_begin(tr, optim, lr, p1, bs, val_data=va, opt_state=self._host_opt_state(), num_models=M,
                       hidden_sizes=self.hidden_sizes)
         self._fit_stepped = False
         try:

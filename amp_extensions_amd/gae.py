@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _native as N
 from .engine import AmxContext, round_up
+from .optstate import baseline_layout, common_step, pack_state, read_state, write_state
 
 
 def init_mlp_baseline_params(inp_dim: int, hidden=(128, 128), seed: int | None = None):
@@ -71,9 +72,7 @@ class DeviceMLPBaseline:
         """Build from an mjrl `MLPBaseline`: its nn.Sequential of Linear/ReLU, batch_size and
         epochs, and its optimizer's hyper-parameters and state (step, exp_avg, exp_avg_sq;
         absent before the optimizer's first step)."""
-        g = baseline.optimizer.param_groups[0]
-        if g.get("amsgrad", False):
-            raise NotImplementedError("the device fit implements Adam without amsgrad")
+        _, g, _ = read_state(baseline.optimizer, kinds=("adam",))
         self = cls(ctx, cls._layers_of(baseline), learn_rate=g["lr"], reg_coef=g["weight_decay"],
                    batch_size=baseline.batch_size, epochs=baseline.epochs, betas=g["betas"], eps=g["eps"])
         if self.fit_supported():  # a shape the fit refuses still predicts; it has no state to load
@@ -105,25 +104,14 @@ class DeviceMLPBaseline:
             self._adam = None  # another model: its moments do not carry over
         self.widths = widths
         self.Hp = [round_up(h, 128) for h in widths]
+        self.layout = baseline_layout(c.S + 4, self.kf, widths, self.Hp)
         self.col = [0, self.kf]
         for hp in self.Hp:
             self.col.append(self.col[-1] + hp)
         self.ldv = self.col[-1]
-        self.W, self.b = [], []
-        k_in, kin_pad = c.S + 4, self.kf
-        for i, (W, b) in enumerate(layers[:-1]):
-            Wp = torch.zeros(self.Hp[i], kin_pad, dtype=torch.float32)
-            Wp[: W.shape[0], :k_in] = torch.as_tensor(W).float()
-            bp = torch.zeros(self.Hp[i], dtype=torch.float32)
-            bp[: W.shape[0]] = torch.as_tensor(b).float()
-            self.W.append(Wp.to(dev).contiguous())
-            self.b.append(bp.to(dev).contiguous())
-            k_in, kin_pad = W.shape[0], self.Hp[i]
-        W, b = layers[-1]
-        wh = torch.zeros(self.Hp[-1], dtype=torch.float32)
-        wh[: W.shape[1]] = torch.as_tensor(W).float().reshape(-1)
-        self.w_head = wh.to(dev).contiguous()
-        self.b_head = torch.as_tensor(b).float().reshape(1).to(dev).contiguous()
+        padded = self.layout.views(self.layout.pack([t for Wb in layers for t in Wb]))
+        *hidden, w_head, self.b_head = [t.to(dev).contiguous() for t in padded]
+        self.W, self.b, self.w_head = hidden[0::2], hidden[1::2], w_head.reshape(-1)
 
     def workspace(self, rows: int) -> torch.Tensor:
         rp = max(round_up(rows, 128), 128)
@@ -175,21 +163,9 @@ class DeviceMLPBaseline:
         if self.batch_size != FIT_BATCH:
             raise NotImplementedError(f"the device fit supports batch_size {FIT_BATCH}, not {self.batch_size}")
 
-    def _param_slices(self):
-        """(offset, padded shape, live shape) of W0, b0, W1, b1, w2, b2 in the Adam moment vectors
-        (amx_vfit_param_count's layout), in torch's parameter order."""
-        k, (h0, h1), (p0, p1) = self.ctx.S + 4, self.widths, self.Hp
-        shapes = [((p0, self.kf), (h0, k)), ((p0,), (h0,)), ((p1, p0), (h1, h0)), ((p1,), (h1,)),
-                  ((1, p1), (1, h1)), ((1,), (1,))]
-        out, o = [], 0
-        for pad, live in shapes:
-            out.append((o, pad, live))
-            o += int(np.prod(pad))
-        return out, o
-
     def _adam_state(self):
         if self._adam is None:
-            _, P = self._param_slices()
+            P = self.layout.size
             assert P == self.ctx.lib.amx_vfit_param_count(self.kf, self.Hp[0], self.Hp[1])
             dev = self.ctx.device
             self._adam = (torch.zeros(P, dtype=torch.float32, device=dev),
@@ -202,21 +178,9 @@ class DeviceMLPBaseline:
         bias per Linear) -> the device moments and step count.  Parameters without state (no
         step taken yet) load as zeros."""
         self._check_fit_supported()
-        params = optimizer.param_groups[0]["params"]
-        slices, P = self._param_slices()
-        if len(params) != len(slices):
-            raise ValueError(f"optimizer holds {len(params)} parameters, the baseline has {len(slices)}")
-        m, v, step = torch.zeros(P), torch.zeros(P), 0
-        for p, (o, pad, live) in zip(params, slices):
-            st = optimizer.state.get(p, {})
-            if not st:
-                continue
-            if tuple(st["exp_avg"].shape) != live:
-                raise ValueError(f"optimizer state of shape {tuple(st['exp_avg'].shape)}, expected {live}")
-            step = int(st["step"])
-            idx = tuple(slice(0, n) for n in live)
-            m[o:o + int(np.prod(pad))].view(pad)[idx] = st["exp_avg"].detach().float().cpu()
-            v[o:o + int(np.prod(pad))].view(pad)[idx] = st["exp_avg_sq"].detach().float().cpu()
+        kind, _, states = read_state(optimizer, kinds=("adam",))
+        step = common_step(states)
+        m, v = pack_state(self.layout, kind, states)
         dm, dv, dstep = self._adam_state()
         dm.copy_(m)
         dv.copy_(v)
@@ -227,20 +191,13 @@ class DeviceMLPBaseline:
         parameter order and live (unpadded) shapes."""
         self._check_fit_supported()
         dm, dv, dstep = self._adam_state()
-        m, v = dm.cpu(), dv.cpu()
-        slices, _ = self._param_slices()
-        cut = lambda x: [x[o:o + int(np.prod(pad))].view(pad)[tuple(slice(0, n) for n in live)].clone()
-                         for o, pad, live in slices]
-        return int(dstep.item()), cut(m), cut(v)
+        return int(dstep.item()), self.layout.unpack(dm.cpu()), self.layout.unpack(dv.cpu())
 
     def layers(self):
         """[(W [out, in], b)] per layer on the host, live shapes (the inverse of sync_from)."""
-        k_in, out = self.ctx.S + 4, []
-        for W, b, h in zip(self.W, self.b, self.widths):
-            out.append((W[:h, :k_in].cpu().clone(), b[:h].cpu().clone()))
-            k_in = h
-        out.append((self.w_head[:k_in].cpu().reshape(1, -1).clone(), self.b_head.cpu().clone()))
-        return out
+        padded = [t for Wb in zip(self.W, self.b) for t in Wb] + [self.w_head, self.b_head]
+        live = self.layout.unpack(torch.cat([t.reshape(-1) for t in padded]).cpu())
+        return list(zip(live[0::2], live[1::2]))
 
     def sync_to(self, baseline) -> None:
         """Write the weights into `baseline.model` and the Adam state into `baseline.optimizer`
@@ -259,12 +216,11 @@ class DeviceMLPBaseline:
             return
         step, ms, vs = self.adam_state()
         opt = baseline.optimizer
-        for p, m, v in zip(opt.param_groups[0]["params"], ms, vs):
-            if step == 0:
+        if step == 0:
+            for p in opt.param_groups[0]["params"]:
                 opt.state.pop(p, None)
-            else:
-                opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.to(p.device).view_as(p),
-                                "exp_avg_sq": v.to(p.device).view_as(p)}
+        else:
+            write_state(opt, "adam", step, ms, vs)
 
     def fit_grid(self, rows: int, T: int, L: int, obs: torch.Tensor, ldo: int, end: torch.Tensor, stride: int,
                  returns: torch.Tensor, lengths: torch.Tensor | None = None, t0: torch.Tensor | None = None,

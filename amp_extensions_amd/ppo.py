@@ -102,9 +102,6 @@ class DevicePPO:
         """(step, [exp_avg per parameter], [exp_avg_sq per parameter]) on the host."""
         return self._bc.adam_state()
 
-    def _trained(self) -> int:
-        return 7
-
     # ---- the update -------------------------------------------------------------------------------
 
     def _eval(self, old, new, obs, act, adv, out) -> None:
@@ -288,7 +285,7 @@ class PPO:
         d.theta_old.copy_(torch.cat([p.data.reshape(-1).float() for p in self.policy.old_params]))
         d.load_optimizer(self.optimizer)
         out = d.train_from_arrays(observations, actions, advantages)
-        write_optimizer(self.optimizer, d)
+        write_optimizer(self.optimizer, d._bc)  # all seven tensors: DeviceBC under MLE
         self.policy.set_param_values(d.theta.cpu().numpy(), set_new=True, set_old=True)
         t_opt = timer.time() - ts
 

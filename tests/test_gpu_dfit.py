@@ -312,10 +312,10 @@ def test_padding_inert_and_deterministic(opt):
     assert not W0[h0:].any() and not W0[:, D:].any() and not b0[h0:].any()
     assert not W1[h1:].any() and not W1[:, h0:].any() and not b1[h1:].any()
     assert not w2[h1:].any() and not b2[1:].any()
+    live = gc.layout.views(gc.layout.live_mask())
     for vec in runs[0][6:]:
-        for off, shape, valid in gc._param_slices():
-            v = vec[off:off + shape[0] * shape[1]].view(shape)
-            assert v[:valid[0], :valid[1]].any() and not v[valid[0]:].any() and not v[:, valid[1]:].any()
+        for v, m in zip(gc.layout.views(vec.cpu()), live):
+            assert v[m].any() and not v[~m].any()
 
 
 def test_zero_rows_and_zero_norms_stay_finite():

@@ -284,15 +284,8 @@ def test_inference_after_training(resumed, tmp_path):
 
 def _pad_masks(eng):
     """Per layer (W mask [N_i][K_i], b mask [N_i]) of the valid (unpadded) entries."""
-    cm = torch.from_numpy(eng._colmap())
-    out = []
-    for i in range(eng.ctx.L + 1):
-        N_, K_, rows, n_in = eng._layer_dims(i)
-        Wm, bm = torch.zeros(N_, K_, dtype=torch.bool), torch.zeros(N_, dtype=torch.bool)
-        Wm[:rows][:, cm[:n_in]] = True
-        bm[:rows] = True
-        out.append((Wm, bm))
-    return out
+    masks = eng.layout.views(eng.layout.live_mask())
+    return list(zip(masks[0::2], masks[1::2]))
 
 
 def test_padding_stays_zero_and_fit_is_deterministic():
@@ -321,7 +314,8 @@ def test_padding_stays_zero_and_fit_is_deterministic():
             for key in ("s1", "s2"):
                 if state[key] is None:
                     continue
-                for i, (Wv, bv) in enumerate(eng._flat_views(state[key])):
+                views = eng.layout.views(state[key])
+                for i, (Wv, bv) in enumerate(zip(views[0::2], views[1::2])):
                     assert not Wv[:, ~masks[i][0]].any() and not bv[:, ~masks[i][1]].any(), (optim, key, i)
                     assert Wv[:, masks[i][0]].abs().max() > 0
             assert state["step"].tolist() == [6] * 4

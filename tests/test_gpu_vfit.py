@@ -143,10 +143,7 @@ def check_returns(out, r32, r64):
 
 def check_padding_is_zero(bl):
     """Everything outside the live blocks of the padded weights, biases and moments is exactly 0."""
-    slices, P = bl._param_slices()
-    live = torch.zeros(P, dtype=torch.bool)
-    for o, pad, lv in slices:
-        live[o:o + int(np.prod(pad))].view(pad)[tuple(slice(0, n) for n in lv)] = True
+    live, P = bl.layout.live_mask(), bl.layout.size
     flat_w = torch.cat([bl.W[0].reshape(-1), bl.b[0], bl.W[1].reshape(-1), bl.b[1], bl.w_head, bl.b_head]).cpu()
     assert flat_w.numel() == P and (~live).sum() > 0
     for name, t in (("weights", flat_w), ("exp_avg", bl._adam[0].cpu()), ("exp_avg_sq", bl._adam[1].cpu())):
