@@ -125,6 +125,13 @@ extern "C" int amx_set_termination(amx_ctx* c, int n_bodies, const int32_t* body
     AMX_CHECK_ARG(shape[i] >= 0 && shape[i] <= 2, "amx_set_termination: shape[%d]=%d", i, shape[i]);
     AMX_CHECK_ARG(off + pos_dim + 1 < c->S || shape[i] == AMX_SHAPE_BOX,
                   "amx_set_termination: body %d indexes past the state (S=%d)", body_id[i], c->S);
+    // check_collision reads ob before check_velocity rescales ob[vel_offset:] in place
+    // (sim_env.py:171-172, 264-267); the step kernel rescales first, so a checked element inside
+    // the velocity block would be read rescaled: refused (the pose block precedes the velocities)
+    AMX_CHECK_ARG(!(vel_check && record_vel_as_pos) || shape[i] == AMX_SHAPE_BOX ||
+                      (shape[i] == AMX_SHAPE_CAPSULE ? off + pos_dim + 1 : off + 1) < vel_offset,
+                  "amx_set_termination: body %d lies inside the rescaled velocity block (vel_offset=%d)", body_id[i],
+                  vel_offset);
     t.shape[i] = shape[i];
     t.y_index[i] = off + 1;                  // sim_env.py:182,185
     t.ny_index[i] = off + pos_dim + 1;       // sim_env.py:213

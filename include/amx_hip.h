@@ -85,7 +85,9 @@ int amx_set_normalizers(amx_ctx* ctx, const float* mu_s, const float* sd_s, cons
  * fall-body tables and ctrl flags, gym-simenv/gym_simenv/envs/sim_env.py:83-115, and
  * is_done/check_velocity's parameters, :164-173, :259-268.  body_id[i] is the
  * character body index; p0/p1 are BodyDefs Param0/Param1 (radius = 0.5*p0, capsule
- * height = p1).  pos_dim/rot_dim: per-body pose feature widths (3 and 6). */
+ * height = p1).  pos_dim/rot_dim: per-body pose feature widths (3 and 6).  With
+ * vel_check and record_vel_as_pos every checked body element must lie below vel_offset
+ * (check_collision reads ob before check_velocity rescales ob[vel_offset:], :171-172). */
 int amx_set_termination(amx_ctx* ctx, int n_bodies, const int32_t* body_id, const int32_t* shape,
                         const double* p0, const double* p1, int record_all_world,
                         int record_world_root_pos, int pos_dim, int rot_dim, int horizon,

@@ -264,3 +264,144 @@ def test_simenv_with_reset_noise_runs(setup):
     assert sum(len(p["rewards"]) for p in paths) >= 60
     with pytest.raises(NotImplementedError):
         amx.BatchedSimEnv(ens, s[:64], lanes=8, reset_args=ra)
+
+
+# ---- reset states under every record flag, with and without the ground resolve, both loop modes ----
+# SimEnv hands RecordWorldRootPos / RecordWorldRootRot / RecordAllWorld of the controller file and
+# reset_args['resolve'] to amx_motion_states and amx_reset_lanes_motion as flag bits 1, 2, 4 and 8;
+# G12 holds flags = 2 and Loop = "wrap" only.  The comparator is the oracle, whose flag branches
+# were read against CtController::BuildStatePose / BuildStateVel (parity section).
+LOOPS = ("wrap", "none")
+
+
+@pytest.fixture(scope="module")
+def flag_setup(golden):
+    """One context per loop mode (a context holds one clip), apart from `setup`'s."""
+    import amp_extensions_amd as amx
+    from amp_extensions_amd.motion import ReferenceMotion
+    g = golden("g12_motion.npz")
+    assert str(g["loop"]) == "wrap"
+    char = json.loads(str(g["character_json"]))
+    J, B, _ = D.load_character(char)
+    out = {}
+    for loop in LOOPS:
+        motion = {"Loop": loop, "Frames": g["frames"].tolist()}
+        ctx = amx.AmxContext(226, 28, n_models=4, hidden=128, n_hidden=1, device=DEV)
+        rm = ReferenceMotion(ctx, char, motion)
+        M = D.Motion(motion, J)
+        assert rm.loop == M.loop == (loop == "wrap")
+        out[loop] = (ctx, rm, J, B, M)
+    out["source"] = (char, {"Loop": "wrap", "Frames": g["frames"].tolist()})
+    return out
+
+
+def flag_times(M, loop):
+    d = M.duration
+    rs = np.random.RandomState(6)
+    if loop == "none":  # clamped before the first frame and after the last (zero velocity past the end)
+        edge = [-1.5, -1e-9, 0.0, d, d * (1 + 1e-12), d + 0.3, 3 * d]
+        return np.concatenate([edge, rs.uniform(0, d, 10)])
+    edge = [-2.3 * d, -3 * d, -d, -0.4, -1e-12, 0.0, d, 2 * d]  # negative cycle counts, exact multiples
+    return np.concatenate([edge, rs.uniform(-2 * d, 3 * d, 10)])
+
+
+_ORACLE_FLAG_STATES = {}
+
+
+def oracle_flag_states(fs, loop, flags, resolve):
+    key = (loop, flags, resolve)
+    if key not in _ORACLE_FLAG_STATES:
+        _, _, J, B, M = fs[loop]
+        ref = np.stack([D.reset_state(J, B, M, float(t), record_world_root_pos=bool(flags & 1),
+                                      record_world_root_rot=bool(flags & 2), record_all_world=bool(flags & 4),
+                                      resolve=resolve) for t in flag_times(M, loop)])
+        ref.setflags(write=False)
+        _ORACLE_FLAG_STATES[key] = ref
+    return _ORACLE_FLAG_STATES[key]
+
+
+def device_states(ctx, times, kernel_flags):
+    from amp_extensions_amd import _native as N
+    t = torch.as_tensor(np.asarray(times, np.float64)).to(DEV).contiguous()
+    out = torch.full((t.numel(), 226), -7.0, dtype=torch.float64, device=DEV)
+    N.check(ctx.lib.amx_motion_states(ctx.h, t.data_ptr(), t.numel(), kernel_flags, out.data_ptr(), 226, ctx.stream),
+            "amx_motion_states")
+    return out
+
+
+@pytest.mark.parametrize("loop", LOOPS)
+@pytest.mark.parametrize("resolve", [True, False])
+@pytest.mark.parametrize("flags", range(8))
+def test_motion_states_every_flag_match_oracle(flag_setup, flags, resolve, loop):
+    ctx, rm, J, B, M = flag_setup[loop]
+    times = flag_times(M, loop)
+    got = device_states(ctx, times, flags | (0 if resolve else 8)).cpu().numpy()
+    ref = oracle_flag_states(flag_setup, loop, flags, resolve)
+    err = np.abs(got - ref) / np.maximum(1.0, np.abs(ref))
+    assert err.max() <= 1e-10, (err.max(), np.unravel_index(err.argmax(), err.shape))
+    if loop == "none":
+        past = times >= M.duration
+        assert past.sum() >= 3 and (ref[past, 136:] == 0).all() and (got[past, 136:] == 0).all()
+        assert np.abs(ref[~past, 136:]).max() > 1e-3
+        # clamped pose: every time before the first frame gives the state at 0, every time past the end the last
+        np.testing.assert_array_equal(got[times <= 0], np.broadcast_to(got[times == 0], got[times <= 0].shape))
+        np.testing.assert_array_equal(got[past], np.broadcast_to(got[times == M.duration], got[past].shape))
+
+
+@pytest.mark.parametrize("loop", LOOPS)
+def test_record_flags_discriminate(flag_setup, loop):
+    """Each flag bit moves the oracle's states by more than 1e-6 over the sampled times, and only in
+    the slots it governs, so a kernel that ignored the bit could not meet 1e-10 under both settings.
+    Bit 1: the root position; bit 2: the root's normal / tangent and its velocities; bit 4: all
+    bodies.  Bit 8 (no ground resolve) moves the root height."""
+    n = 15
+    base = 1 + 9 * n
+    slots = {1: list(range(1, 4)), 2: list(range(4, 10)) + list(range(base, base + 6)), 4: list(range(1, 226))}
+    for bit, bases in ((1, (0, 2)), (2, (0, 1)), (4, (0, 1, 2, 3))):
+        for f in bases:
+            a = oracle_flag_states(flag_setup, loop, f, True)
+            b = oracle_flag_states(flag_setup, loop, f | bit, True)
+            diff = np.abs(a - b).max(0)
+            rest = np.setdiff1d(np.arange(226), slots[bit])
+            assert diff[slots[bit]].max() > 1e-6 and (diff[rest] == 0).all(), (bit, f)
+            if bit == 4:  # bodies other than the root move too
+                assert diff[10:base].max() > 1e-6 and diff[base + 6:].max() > 1e-6
+    for f in range(8):
+        a, b = oracle_flag_states(flag_setup, loop, f, True), oracle_flag_states(flag_setup, loop, f, False)
+        assert np.abs(a[:, 0] - b[:, 0]).max() > 1e-6
+
+
+@pytest.mark.parametrize("loop", LOOPS)
+def test_reset_lanes_motion_every_flag_equals_motion_states(flag_setup, loop):
+    """amx_reset_lanes_motion under each of the 16 flag sets == amx_motion_states at its t_out, bit for bit."""
+    from amp_extensions_amd import _native as N
+    ctx, rm, J, B, M = flag_setup[loop]
+    L = 70
+    for kf in range(16):
+        ob = torch.full((L, 226), -7.0, dtype=torch.float64, device=DEV)
+        ns = torch.full((L,), 7, dtype=torch.int32, device=DEV)
+        mi = torch.zeros(L, dtype=torch.int32, device=DEV)
+        rc = torch.zeros(L, dtype=torch.int32, device=DEV)
+        tout = torch.zeros(L, dtype=torch.float64, device=DEV)
+        N.check(ctx.lib.amx_reset_lanes_motion(ctx.h, None, None, 99 + kf, 0.0, kf, ob.data_ptr(), ob.data_ptr(),
+                                               ns.data_ptr(), mi.data_ptr(), rc.data_ptr(), tout.data_ptr(), L,
+                                               ctx.stream), "amx_reset_lanes_motion")
+        t = tout.cpu().numpy()
+        assert (t >= 0).all() and (t < M.duration).all() and len(np.unique(t)) == L
+        assert torch.equal(ob, device_states(ctx, t, kf)), kf
+        assert (ns == 0).all() and (rc == 1).all()
+
+
+def test_kernel_flags_carry_the_resolve_bit(flag_setup):
+    from amp_extensions_amd.motion import ReferenceMotion
+    ctx, rm, J, B, M = flag_setup["wrap"]
+    char, motion = flag_setup["source"]
+    assert rm.kernel_flags == 2 and rm.flags == 2  # the constructor's defaults: world root rotation, resolve
+    for f in range(8):
+        for resolve in (True, False):  # (the same clip again: the context's motion does not change)
+            r = ReferenceMotion(ctx, char, motion, record_world_root_pos=bool(f & 1), record_world_root_rot=bool(f & 2),
+                                record_all_world=bool(f & 4), resolve=resolve)
+            assert r.flags == f and r.kernel_flags == f | (0 if resolve else 8)
+            assert bool(r.kernel_flags & 8) == (not resolve)
+    t = flag_times(M, "wrap")[:6]
+    assert torch.equal(r.states(t), device_states(ctx, t, 7 | 8))  # states() passes kernel_flags
