@@ -1,10 +1,10 @@
 """amp_extensions_amd — MI355X-native learned-dynamics rollout path of amp_extensions.
 
 The gym_simenv learned-dynamics step (4-model dense-MLP ensemble), the MILO RFF-MMD
-cost with the ensemble-disagreement bonus, the AMP/GAIL least-squares discriminator
+cost and its MLP-feature variant with the ensemble-disagreement bonus, the AMP/GAIL least-squares discriminator
 reward and the humanoid3d fall/horizon termination, as hand-written HIP kernels for
 gfx950 behind a C ABI (include/amx_hip.h, libamx_hip.so) and the reference's Python
-surfaces (SimEnv, sample_points, RBFLinearCost, GAILCost, DynamicsEnsemble), plus the
+surfaces (SimEnv, sample_points, RBFLinearCost, MLPCost, GAILCost, DynamicsEnsemble), plus the
 sampler's consumers: returns, MLP value baseline (prediction and the mini-batch Adam fit) and
 GAE (mjrl process_samples, MLPBaseline), the NPG and PPO policy updates (mjrl npg_cg, ppo_clip)
 and the behaviour-cloning warm start (mjrl BC).
@@ -14,7 +14,8 @@ The native library is loaded on first use; there is no CPU fallback.
 from .humanoid import TerminationConfig  # noqa: F401
 
 __all__ = [
-    "AmxContext", "DeviceEnsemble", "RffMap", "RolloutEngine", "RBFLinearCost", "GAILCost", "DevicePolicy",
+    "AmxContext", "DeviceEnsemble", "RffMap", "MlpMap", "RolloutEngine", "RBFLinearCost", "MLPCost", "GAILCost",
+    "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
     "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
     "PPO", "DevicePPO",
@@ -22,10 +23,10 @@ __all__ = [
 
 
 def __getattr__(name):
-    if name in ("AmxContext", "DeviceEnsemble", "RffMap"):
+    if name in ("AmxContext", "DeviceEnsemble", "RffMap", "MlpMap"):
         from . import engine
         return getattr(engine, name)
-    if name in ("RBFLinearCost", "GAILCost"):
+    if name in ("RBFLinearCost", "MLPCost", "GAILCost"):
         from . import costs
         return getattr(costs, name)
     if name == "AgentReplayBuffer":

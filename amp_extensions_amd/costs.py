@@ -1,6 +1,7 @@
 """Device-backed drop-ins for the reference cost objects.
 
 * `RBFLinearCost` — milo/milo/linear_cost.py:6-152 (MILO RFF MMD cost + pessimism bonus)
+* `MLPCost`       — milo/milo/linear_cost.py:154-301: the same cost over MLP features
 * `GAILCost`      — milo/milo/gail_cost.py:44-279: the AMP discriminator's reward + bonus and
                     its training step (update_disc, compute_chi2_distance) on the device.
 
@@ -65,6 +66,16 @@ def _check_input_type(input_type: str, motion) -> None:
         raise ValueError("input_type 'amp' needs the ReferenceMotion (motion=...)")
 
 
+def fit_bandwidth(data: torch.Tensor, bw_samples: int, quantile: float) -> float:
+    """The median-heuristic bandwidth of both MMD costs (linear_cost.py:73-82, 224-230): two
+    torch.randint draws from the global generator, then the quantile of the pair distances."""
+    n = data.shape[0]
+    i0 = torch.randint(low=0, high=n, size=(bw_samples,))
+    i1 = torch.randint(low=0, high=n, size=(bw_samples,))
+    norm = torch.norm(data[i0, :] - data[i1, :], dim=1)
+    return torch.quantile(norm, q=quantile).item()
+
+
 class RBFLinearCost:
     """MMD cost with random-Fourier-feature representations (linear_cost.py:6-152).
 
@@ -103,8 +114,14 @@ class RBFLinearCost:
         if ctx is None:
             S = input_dim // 2 if input_type == "ss" else input_dim
             ctx = AmxContext(S, 1, n_models=1, hidden=128, n_hidden=0, feat_dim=feature_dim, device=device)
+        self._embed_expert(ctx, RffMap(ctx, self.rff_weight, self.rff_bias, gemm=gemm), expert_cpu)
+
+    def _embed_expert(self, ctx: AmxContext, fmap, expert_cpu: torch.Tensor) -> None:
+        """The constructor's device half (no RNG is drawn here): the feature map, the expert
+        features and phi_e, the relabel's buffers."""
+        lambda_b = self.lambda_b
         self.ctx = ctx
-        self.map = RffMap(ctx, self.rff_weight, self.rff_bias, gemm=gemm)
+        self.map = fmap
         self.w = None
         # expert features resident in HBM (:61-62); phi_e from fp64 column sums
         phi, tot = self.map.embed(expert_cpu)
@@ -126,11 +143,7 @@ class RBFLinearCost:
 
     # linear_cost.py:73-82
     def fit_bandwidth(self, data: torch.Tensor) -> float:
-        n = data.shape[0]
-        i0 = torch.randint(low=0, high=n, size=(self.bw_samples,))
-        i1 = torch.randint(low=0, high=n, size=(self.bw_samples,))
-        norm = torch.norm(data[i0, :] - data[i1, :], dim=1)
-        return torch.quantile(norm, q=self.quantile).item()
+        return fit_bandwidth(data, self.bw_samples, self.quantile)
 
     def get_rep(self, x: torch.Tensor) -> torch.Tensor:
         """linear_cost.py:64-71."""
@@ -315,6 +328,90 @@ class RBFLinearCost:
         rff_cost = self.get_costs(x)
         return cost.view(-1, 1), {"bonus": wb.view(-1, 1), "ipm": ipm.view(-1, 1), "v_targ": rff_cost,
                                   "cost": cost.view(-1, 1)}
+
+
+def check_mlp_cost_config(hidden_dims, activation: str, feature_dim: int) -> None:
+    """Refuse what MLPCost does not run on the device; raises before anything is built."""
+    if activation != "relu":
+        raise NotImplementedError(f"MLPCost on the device supports activation='relu' (both run.py branches); got "
+                                  f"{activation!r} (the reference maps every other name to Tanh)")
+    hidden_dims = list(hidden_dims)
+    if len(hidden_dims) == 1 and hidden_dims[0] != feature_dim:
+        raise NotImplementedError(
+            f"hidden_dims={hidden_dims} with feature_dim={feature_dim}: with one hidden width the reference's net is "
+            f"Linear(D, {hidden_dims[0]}) + Tanh alone (linear_cost.py:200-210 adds the feature layer only from the "
+            f"second width on), so it emits features of width {hidden_dims[0]} yet scales them by "
+            f"sqrt(2 / {feature_dim}); this quirk is not reproduced")
+    if feature_dim <= 0 or feature_dim % 128:
+        raise ValueError("feature_dim must be a multiple of 128 for the MFMA feature path")
+
+
+def mlp_cost_net(input_dim: int, hidden_dims, feature_dim: int) -> nn.Sequential:
+    """MLPCost's net on the host (linear_cost.py:199-212), ReLU between the layers: Linear(D, h0),
+    [ReLU, Linear] per further hidden width, ReLU, Linear(., F), Tanh -- or Linear(D, F), Tanh
+    without hidden widths.  The nn.Linear layers draw from torch's global generator in order, and
+    the state_dict keys are the reference's ('0.weight', '2.weight', ...)."""
+    hidden_dims = list(hidden_dims)
+    dim = feature_dim if not hidden_dims else hidden_dims[0]
+    layers = [nn.Linear(input_dim, dim)]
+    if hidden_dims[1:]:
+        for size in hidden_dims[1:]:
+            layers += [nn.ReLU(), nn.Linear(dim, size)]
+            dim = size
+        layers += [nn.ReLU(), nn.Linear(dim, feature_dim)]
+    layers.append(nn.Tanh())
+    return nn.Sequential(*layers)
+
+
+class MLPCost(RBFLinearCost):
+    """MMD cost with MLP feature representations (linear_cost.py:154-301): phi(x) =
+    cos(tanh(net(x))) sqrt(2/F) with a randomly initialised, untrained `net`.  After phi the
+    algorithm is RBFLinearCost's, so everything but the feature map (MlpMap: the hidden layers on
+    the f16x3 GEMM, the last Linear in amx_mlp_features_h3) is inherited: the resident expert
+    features, phi_e and w from fp64 column sums, the clamp, the disagreement bonus, the expert
+    cost and its sharding."""
+
+    def __init__(self, expert_data: torch.Tensor, hidden_dims=[2048, 2048], activation="relu", feature_dim=1024,
+                 input_type="ss", cost_range=[-1., 0.], bw_quantile=0.1, bw_samples=100000, lambda_b=1.0, lr=0.0,
+                 seed=100, ctx: AmxContext | None = None, device="cuda", motion=None):
+        """The reference's constructor arguments, then `ctx` / `device` / `motion` as RBFLinearCost.
+        RNG order as the reference: the seeds, the nn.Linear layers in order, then the bandwidth
+        draw (after the net here).  `net` stays on the host with the reference's keys, so
+        save_checkpoint's cost_function.net.state_dict() (milo/utils.py:32-37) works as written."""
+        _check_input_type(input_type, motion)
+        check_mlp_cost_config(hidden_dims, activation, feature_dim)
+        from .engine import MlpMap
+        torch.manual_seed(seed)          # linear_cost.py:187-188
+        np.random.seed(seed)
+        expert_cpu = expert_data.detach().float().cpu()
+        input_dim = expert_cpu.size(1)
+        self.expert_data = expert_data
+        self.input_type = input_type
+        self.input_dim = input_dim
+        self.motion = motion
+        self.feature_dim = feature_dim
+        self.hidden_dims = list(hidden_dims)
+        self.cost_range = cost_range
+        if cost_range is not None:
+            self.c_min, self.c_max = float(cost_range[0]), float(cost_range[1])
+        self.lambda_b = float(lambda_b)
+        self.lr = lr
+        self.activation = nn.ReLU()
+        self.net = mlp_cost_net(input_dim, hidden_dims, feature_dim)      # :199-212
+        self.quantile = bw_quantile
+        self.bw_samples = bw_samples
+        self.bw = self.fit_bandwidth(expert_cpu)                            # :217 (unused by the features)
+        if ctx is None:
+            S = input_dim // 2 if input_type == "ss" else input_dim
+            ctx = AmxContext(S, 1, n_models=1, hidden=128, n_hidden=0, feat_dim=feature_dim, device=device)
+        linears = [m for m in self.net if isinstance(m, nn.Linear)]
+        self._embed_expert(ctx, MlpMap(ctx, [(m.weight.data, m.bias.data) for m in linears]), expert_cpu)
+
+    def get_expert_cost(self) -> torch.Tensor:
+        """linear_cost.py:255-259 over the resident expert features."""
+        if self.cost_range is None:   # the reference indexes cost_range, None without a range
+            raise TypeError("'NoneType' object is not subscriptable")
+        return super().get_expert_cost()
 
 
 def plan_disc_batch(n_rb: int, n_expert: int, bs: int, sample_rb: bool):

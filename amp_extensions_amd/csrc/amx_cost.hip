@@ -89,7 +89,8 @@ __global__ __launch_bounds__(256) void k_mmd_fit(const double* __restrict__ phi_
   if (threadIdx.x == 0) *mmd = (float)(red[0] + red[1] + red[2] + red[3]);
 }
 
-// dot(phi[row], w) over F (F % 256 == 0 handled by float4 x 64 lanes per 256 floats)
+// dot(phi[row], w) over F (float4 x 64 lanes per 256 floats; any F % 4 == 0: in a last, partial
+// chunk the lanes past F add nothing -- the entry points take F % 128 == 0, MLPCost's F = 128)
 __device__ inline double row_dot(const float* __restrict__ row, const float* __restrict__ w, int F, int lane) {
   double s = 0.0;
   for (int f = lane * 4; f < F; f += 256) {
@@ -424,7 +425,7 @@ static int mmd_reward(bool clamp, amx_ctx* ctx, const float* phi, int ldphi, con
                       float thr, double lambda_b, float c_min, float c_max, float* reward, float* ipm, float* wbonus,
                       int n, void* stream) {
   AMX_CHECK_ARG(ctx && phi && w && disc && reward, "amx_mmd_reward: null pointer");
-  AMX_CHECK_ARG(F > 0 && F % 256 == 0 && ldphi >= F && ldphi % 4 == 0, "amx_mmd_reward: F=%d ldphi=%d", F, ldphi);
+  AMX_CHECK_ARG(F > 0 && F % 128 == 0 && ldphi >= F && ldphi % 4 == 0, "amx_mmd_reward: F=%d ldphi=%d", F, ldphi);
   AMX_CHECK_ARG(amx::aligned16(phi) && amx::aligned16(w), "amx_mmd_reward: phi/w must be 16-byte aligned");
   AMX_CHECK_ARG(n >= 0, "amx_mmd_reward: n=%d", n);
   if (n == 0) return AMX_OK;
@@ -465,7 +466,7 @@ extern "C" int amx_expert_cost(amx_ctx* ctx, const float* phi_e_rows, int ldphi,
                                float c_min, float c_max, double* out, float* mean_out, double lambda_b,
                                void* stream) {
   AMX_CHECK_ARG(ctx && phi_e_rows && w && out, "amx_expert_cost: null pointer");
-  AMX_CHECK_ARG(F > 0 && F % 256 == 0 && ldphi >= F && ldphi % 4 == 0, "amx_expert_cost: F=%d ldphi=%d", F, ldphi);
+  AMX_CHECK_ARG(F > 0 && F % 128 == 0 && ldphi >= F && ldphi % 4 == 0, "amx_expert_cost: F=%d ldphi=%d", F, ldphi);
   AMX_CHECK_ARG(n > 0, "amx_expert_cost: n=%d", n);
   // partials live in out[1 .. nb]; out must hold 1 + 1024 doubles
   const int nb = expert_blocks(n);
@@ -552,7 +553,7 @@ extern "C" int amx_mmd_relabel(amx_ctx* ctx, const double* msg, double count, co
                                const float* expert_rows, int ld_e, int n_e, double* expert_out, float* expert_mean,
                                uint32_t* counter, void* stream) {
   AMX_CHECK_ARG(ctx && msg && phi_e && w && mmd, "amx_mmd_relabel: null pointer");
-  AMX_CHECK_ARG(F > 0 && F % 256 == 0 && F <= 4096, "amx_mmd_relabel: F=%d (multiple of 256, <= 4096)", F);
+  AMX_CHECK_ARG(F > 0 && F % 128 == 0 && F <= 4096, "amx_mmd_relabel: F=%d (multiple of 128, <= 4096)", F);
   AMX_CHECK_ARG(count >= 0.0, "amx_mmd_relabel: count=%g (0: read msg[F])", count);
   AMX_CHECK_ARG(n >= 0 && (n == 0 || (phi && disc && reward && ldphi >= F && ldphi % 4 == 0 && amx::aligned16(phi))),
                 "amx_mmd_relabel: rollout rows n=%d need phi/disc/reward, ldphi=%d", n, ldphi);
@@ -569,8 +570,9 @@ extern "C" int amx_mmd_relabel(amx_ctx* ctx, const double* msg, double count, co
   a.eout = expert_out; a.emean = expert_mean; a.escale = (float)(1.0 - lambda_b); a.counter = counter;
   const size_t lds = (size_t)F * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  // NC = F/256 chunks per lane for F <= 1024 (R rows per round trip), else the generic path
-  const int nc = F <= 1024 ? F / 256 : 0;
+  // NC = F/256 chunks per lane for F <= 1024 in whole chunks (R rows per round trip), else the
+  // generic path
+  const int nc = (F <= 1024 && F % 256 == 0) ? F / 256 : 0;
 #define AMX_RELABEL_CASE(NC)                                                                              \
   case NC: {                                                                                              \
     constexpr int R = relabel_rows<NC>();                                                                 \

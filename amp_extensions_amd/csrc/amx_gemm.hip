@@ -99,6 +99,16 @@ __device__ __forceinline__ float rff_cos(float z) {
   return __builtin_amdgcn_cosf(r * 0.15915494309189535f);
 }
 
+// the feature value of a pre-activation z: torch.cos(z) * np.sqrt(2/F) (EPI_RFF: two fp32
+// roundings, as torch) or cos(tanh(z)) * sqrt(2/F) (EPI_MLPF, see mlp_feature)
+template <int EPI>
+__device__ __forceinline__ float feature_of(float z, float scale) {
+  if constexpr (EPI == EPI_MLPF)
+    return mlp_feature(z, scale);
+  else
+    return rff_cos(z) * scale;
+}
+
 template <int EPI, class TL>
 __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[TL::TM][TL::TN], int g, int tm, int tn) {
   constexpr int BM = TL::BM, BN = TL::BN, TM = TL::TM, TN = TL::TN;
@@ -185,7 +195,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[TL::TM
       for (int i = 0; i < 32; ++i) {
         const int r = part * 32 + i;
         const float z = Cs[r * CLD + c] + bv;       // nn.Linear: x W^T + b
-        const float phi = rff_cos(z) * a.rff_scale;  // torch.cos(.) * np.sqrt(2/F)
+        const float phi = feature_of<EPI>(z, a.rff_scale);
         Cg[(long long)(row0 + i) * a.ldc + col] = phi;
         csum += ((vmask >> i) & 1u) ? (double)phi : 0.0;
       }
@@ -227,7 +237,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[TL::TM
         const int r = part * PR + i;
         const int row = tm * BM + r;
         const float z = Cs[r * CLD + c] + bv;       // nn.Linear: x W^T + b
-        const float phi = rff_cos(z) * a.rff_scale;  // torch.cos(.) * np.sqrt(2/F)
+        const float phi = feature_of<EPI>(z, a.rff_scale);
         Cg[(long long)row * a.ldc + col] = phi;
         csum += ((vmask >> i) & 1u) ? (double)phi : 0.0;
       }
@@ -535,7 +545,7 @@ __device__ __forceinline__ void epilogue_h3_impl(const GemmArgs& a, f32x16 (&acc
 template <int EPI, class TL>
 __device__ __forceinline__ void epilogue_h3(const GemmArgs& a, f32x16 (&acc)[TL::TM][TL::TN], const int* sExp, int g,
                                             int tm, int tn) {
-  if constexpr (EPI == EPI_RFF) {
+  if constexpr (epi_feature<EPI>) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / TL::WN, wn = wave % TL::WN, li = lane & 31, lh = lane >> 5;
     const int* wexp = a.w_exp + (long long)g * a.strideWexp;
@@ -550,7 +560,7 @@ __device__ __forceinline__ void epilogue_h3(const GemmArgs& a, f32x16 (&acc)[TL:
               acc[m][n][e], sExp[wm * TL::TM * 32 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh] + ec);
     }
     __syncthreads();  // every wave is done with the stage buffers (and with sExp)
-    epilogue<EPI_RFF, TL>(a, acc, g, tm, tn);
+    epilogue<EPI, TL>(a, acc, g, tm, tn);
   } else {
     epilogue_h3_impl<EPI, TL>(a, acc, sExp, g, tm, tn);
   }
@@ -666,7 +676,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
   const float* bias = a.bias + (long long)g * a.strideBias;
   const int* wexp = a.w_exp + (long long)g * a.strideWexp;
   float* Cg = a.C + (long long)g * a.strideC;
-  if constexpr (EPI == EPI_RFF) {  // the 32x32 path's RFF epilogue on the 16x16 accumulator layout
+  if constexpr (epi_feature<EPI>) {  // the 32x32 path's RFF epilogue on the 16x16 accumulator layout
     // The tile staged through LDS in passes of RP rows (all of it when it fits the launch's
     // LDS, TL::RFF_ROWS), then one column per thread: the NT / BN threads of a column take the
     // 32-row groups g = part, part + NT / BN, ... (wave-uniform: BN >= 64), each group's phi
@@ -715,7 +725,7 @@ __device__ __forceinline__ void epilogue_h3_m16(const GemmArgs& a, f32x4 (&acc)[
 #pragma unroll 8
         for (int i = 0; i < AMX_RFF_PART_ROWS; ++i) {
           const float z = Cs[(gl * AMX_RFF_PART_ROWS + i) * CLD + c] + bv;  // nn.Linear: x W^T + b
-          const float phi = rff_cos(z) * a.rff_scale;                       // torch.cos(.) * np.sqrt(2/F)
+          const float phi = feature_of<EPI>(z, a.rff_scale);
           a.C[(long long)(row0 + i) * a.ldc + col] = phi;
           csum += ((vmask >> i) & 1u) ? (double)phi : 0.0;
         }
@@ -1458,7 +1468,7 @@ int launch(void (*kernel)(GemmArgs), GemmArgs& a, hipStream_t stream) {
   const int tiles = a.tiles_m * a.tiles_n * a.groups;
   if (tiles == 0) return AMX_OK;
   constexpr size_t rff_lds = rff_epi_lds(TL::RFF_ROWS, TL::BN);
-  constexpr size_t lds = (EPI == EPI_RFF && TL::LDS < rff_lds) ? rff_lds : TL::LDS;
+  constexpr size_t lds = (epi_feature<EPI> && TL::LDS < rff_lds) ? rff_lds : TL::LDS;
   hipLaunchKernelGGL(kernel, dim3(a.streamk ? a.streamk : tiles), dim3(TL::NT), lds, stream, a);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
@@ -1898,16 +1908,17 @@ extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_
   return launch_h3<EPI_UNNORM, H128>(a, s);
 }
 
-extern "C" int amx_rff_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, int K, const float* x, int ldx,
-                                   const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b,
-                                   float scale, float* phi, int ldphi, double* col_partials, const uint8_t* row_mask,
-                                   void* stream) {
-  AMX_CHECK_ARG(ctx, "amx_rff_features_h3: null ctx");
-  int rc = check_h3("amx_rff_features_h3", 1, rows, K, x, ldx, W2, 0, w_exp, row_exp, 1);
+// The two f16x3 feature layers (EPI_RFF, EPI_MLPF): one argument check and one tile dispatch.
+template <int EPI>
+static int features_h3(const char* fn, amx_ctx* ctx, int rows, int n_valid, int F, int K, const float* x, int ldx,
+                       const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b, float scale,
+                       float* phi, int ldphi, double* col_partials, const uint8_t* row_mask, void* stream) {
+  AMX_CHECK_ARG(ctx, "%s: null ctx", fn);
+  int rc = check_h3(fn, 1, rows, K, x, ldx, W2, 0, w_exp, row_exp, 1);
   if (rc) return rc;
-  AMX_CHECK_ARG(F > 0 && F % 128 == 0, "amx_rff_features_h3: F=%d must be a multiple of 128", F);
-  AMX_CHECK_ARG(b && phi && col_partials && ldphi >= F, "amx_rff_features_h3: null b/phi/partials or ldphi");
-  AMX_CHECK_ARG(n_valid >= 0 && n_valid <= rows, "amx_rff_features_h3: n_valid=%d rows=%d", n_valid, rows);
+  AMX_CHECK_ARG(F > 0 && F % 128 == 0, "%s: F=%d must be a multiple of 128", fn, F);
+  AMX_CHECK_ARG(b && phi && col_partials && ldphi >= F, "%s: null b/phi/partials or ldphi", fn);
+  AMX_CHECK_ARG(n_valid >= 0 && n_valid <= rows, "%s: n_valid=%d rows=%d", fn, n_valid, rows);
   GemmArgs a = {};
   a.A = x; a.lda = ldx;
   a.W2 = W2; a.w_exp = w_exp;
@@ -1919,13 +1930,29 @@ extern "C" int amx_rff_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, i
   if (K % 32 == 0) {
     // 160 x 256 tiles where they fill the CUs in whole rounds (see H160x256r)
     if (rows % 160 == 0 && F % 256 == 0 && ((long long)(rows / 160) * (F / 256)) % ctx->n_cus == 0)
-      return launch_h3<EPI_RFF, H160x256r>(a, (hipStream_t)stream);
+      return launch_h3<EPI, H160x256r>(a, (hipStream_t)stream);
     // (at 40 960 rows the 128 x 128 tile is faster: 121 vs 145 us under the profiler)
-    if ((rows / 128) * (F / 128) < ctx->n_cus && F % 64 == 0) return launch_h3<EPI_RFF, H128x64k32>(a, (hipStream_t)stream);
-    if ((long long)(rows / 128) * (F / 128) > 2LL * ctx->n_cus) return launch_h3<EPI_RFF, H128rff3>(a, (hipStream_t)stream);
-    return launch_h3<EPI_RFF, H128k32>(a, (hipStream_t)stream);
+    if ((rows / 128) * (F / 128) < ctx->n_cus && F % 64 == 0) return launch_h3<EPI, H128x64k32>(a, (hipStream_t)stream);
+    if ((long long)(rows / 128) * (F / 128) > 2LL * ctx->n_cus) return launch_h3<EPI, H128rff3>(a, (hipStream_t)stream);
+    return launch_h3<EPI, H128k32>(a, (hipStream_t)stream);
   }
-  return launch_h3<EPI_RFF, H128>(a, (hipStream_t)stream);
+  return launch_h3<EPI, H128>(a, (hipStream_t)stream);
+}
+
+extern "C" int amx_rff_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, int K, const float* x, int ldx,
+                                   const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b,
+                                   float scale, float* phi, int ldphi, double* col_partials, const uint8_t* row_mask,
+                                   void* stream) {
+  return features_h3<EPI_RFF>("amx_rff_features_h3", ctx, rows, n_valid, F, K, x, ldx, W2, w_exp, row_exp, b, scale,
+                              phi, ldphi, col_partials, row_mask, stream);
+}
+
+extern "C" int amx_mlp_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, int K, const float* x, int ldx,
+                                   const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b,
+                                   float scale, float* phi, int ldphi, double* col_partials, const uint8_t* row_mask,
+                                   void* stream) {
+  return features_h3<EPI_MLPF>("amx_mlp_features_h3", ctx, rows, n_valid, F, K, x, ldx, W2, w_exp, row_exp, b, scale,
+                               phi, ldphi, col_partials, row_mask, stream);
 }
 
 extern "C" int amx_set_gemm_timer(amx_ctx* ctx, uint64_t* buf) {

@@ -11,7 +11,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // native vector (HIP's float4 is a wrapper struct: arrays of it were not promoted to registers)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { EPI_BIAS_ACT = 0, EPI_UNNORM = 1, EPI_RFF = 2 };
+// EPI_MLPF: the feature layer of the MLP-feature MMD cost (MLPCost): EPI_RFF's staging, phi rows
+// and fp64 column partials with phi = cos(tanh(z)) * scale in place of cos(z) * scale
+enum { EPI_BIAS_ACT = 0, EPI_UNNORM = 1, EPI_RFF = 2, EPI_MLPF = 3 };
+// the two feature epilogues (compile-time: the other kinds' kernels do not see them)
+template <int EPI> constexpr bool epi_feature = EPI == EPI_RFF || EPI == EPI_MLPF;
 
 struct GemmArgs {
   const float* A; long long strideA; int lda;
@@ -20,12 +24,12 @@ struct GemmArgs {
   float* C; long long strideC; int ldc; int col_off;
   int rows, N, K;
   int act;                 // EPI_BIAS_ACT: AMX_ACT_*
-  int n_valid;             // EPI_UNNORM: valid output columns; EPI_RFF: valid rows
+  int n_valid;             // EPI_UNNORM: valid output columns; EPI_RFF / EPI_MLPF: valid rows
   const float* scale;      // EPI_UNNORM: sd_d
   const float* shift;      // EPI_UNNORM: mu_d
-  float rff_scale;         // EPI_RFF: sqrt(2/F)
-  double* col_partials;    // EPI_RFF: [rows/128][N]
-  const uint8_t* row_mask; // EPI_RFF: nullable
+  float rff_scale;         // EPI_RFF / EPI_MLPF: sqrt(2/F)
+  double* col_partials;    // EPI_RFF / EPI_MLPF: [rows/32][N] (AMX_RFF_PART_ROWS)
+  const uint8_t* row_mask; // EPI_RFF / EPI_MLPF: nullable
   int tiles_m, tiles_n, groups;
   const uint16_t* W3;      // bf16x6 path: 3-limb weight image [g][N][K/16][3][16] (amx_split_bf16x3)
   long long strideW3;      //   elements between groups; a row is 3*K elements
@@ -105,6 +109,58 @@ __device__ __forceinline__ int exp_of_bits(uint32_t absbits) {
   int e = (int)(absbits >> 23) - 126;
   e = e < -100 ? -100 : e;
   return e > 100 ? 100 : e;
+}
+
+// phi = cos(tanh(z)) * scale of MLPCost.get_rep (milo/milo/linear_cost.py:232-237: the net ends
+// in Tanh, then torch.cos(.) * np.sqrt(2/F)), evaluated in fp64 and rounded to fp32 once.  phi of
+// a default-initialised net sits within a few ulp of scale and w = mean phi_pi - mean phi_e is a
+// difference of nearly equal means, so the budget is a fraction of an ulp of phi: rff_cos (3.5e-7
+// absolute) and a 1-2 ulp fp32 tanh are both too coarse.  fp64 FMAs run at the fp32 rate on
+// CDNA4's vector pipe and the epilogue is ~35 of them per element beside the K-loop's MFMAs.
+//   tanh(z) = 1 - 2 / (e^2z + 1): e^2z = 2^n e^r with n = rint(2z / ln 2), |r| <= ln 2 / 2 (ln 2
+//     in two parts, fma) and the degree-10 Taylor polynomial of e^r (r^11 / 11! < 3e-13); the
+//     cancellation at small z is absolute (1e-16), which is what cos(t) needs (|dcos/dt| <= |t|);
+//     2z is clamped to +-50 (tanh = +-1 to fp64 rounding), a NaN passes through both compares;
+//   cos(t), |t| <= 1: the even Taylor polynomial through t^16 / 16! (next term 1.6e-16).
+// Measured against long double over z in [-12, 12] and at the fp32 extremes: |error| <= 0.5 ulp
+// of the fp32 result + 2e-16.  Host-callable, so the same code is checked on the CPU.
+__host__ __device__ __forceinline__ float mlp_feature(float z, float scale) {
+  double x = 2.0 * (double)z;
+  x = x > 50.0 ? 50.0 : x;
+  x = x < -50.0 ? -50.0 : x;
+  const double n = __builtin_rint(x * 1.4426950408889634);
+  double r = __builtin_fma(-n, 0.6931471803691238, x);  // ln 2: high part (low 21 bits clear: n * hi exact)
+  r = __builtin_fma(-n, 1.9082149292705877e-10, r);
+  double p = 2.7557319223985893e-07;                     // 1/10!
+  p = __builtin_fma(p, r, 2.7557319223985888e-06);
+  p = __builtin_fma(p, r, 2.4801587301587302e-05);
+  p = __builtin_fma(p, r, 1.9841269841269841e-04);
+  p = __builtin_fma(p, r, 1.3888888888888889e-03);
+  p = __builtin_fma(p, r, 8.3333333333333332e-03);
+  p = __builtin_fma(p, r, 4.1666666666666664e-02);
+  p = __builtin_fma(p, r, 1.6666666666666666e-01);
+  p = __builtin_fma(p, r, 0.5);
+  p = __builtin_fma(p, r, 1.0);
+  p = __builtin_fma(p, r, 1.0);
+  const double d = __builtin_ldexp(p, (int)n) + 1.0;    // e^2z + 1 in [1, 5.2e21]
+#if defined(__HIP_DEVICE_COMPILE__)
+  double q = __builtin_amdgcn_rcp(d);                    // v_rcp_f64 + one Newton step
+  q = __builtin_fma(__builtin_fma(-d, q, 1.0), q, q);
+#else
+  const double q = 1.0 / d;
+#endif
+  const double t = __builtin_fma(-2.0, q, 1.0);
+  const double s = t * t;
+  double c = 4.7794773323873853e-14;                     // 1/16!
+  c = __builtin_fma(c, s, -1.1470745597729725e-11);      // -1/14!
+  c = __builtin_fma(c, s, 2.08767569878681e-09);         // 1/12!
+  c = __builtin_fma(c, s, -2.7557319223985888e-07);      // -1/10!
+  c = __builtin_fma(c, s, 2.4801587301587302e-05);       // 1/8!
+  c = __builtin_fma(c, s, -1.3888888888888889e-03);      // -1/6!
+  c = __builtin_fma(c, s, 4.1666666666666664e-02);       // 1/4!
+  c = __builtin_fma(c, s, -0.5);
+  c = __builtin_fma(c, s, 1.0);
+  return (float)(c * (double)scale);
 }
 
 // LDS of the RFF epilogue: a staged rows x (BN + 4) f32 tile

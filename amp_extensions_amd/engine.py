@@ -587,6 +587,8 @@ class DeviceEnsemble:
 class RffMap:
     """phi(x) = cos(x W^T + b) * sqrt(2/F) on MFMA (linear_cost.py:64-71) with fp64 column sums."""
 
+    step_invariant = True  # one launch whose per-row work does not depend on the row count
+
     def __init__(self, ctx: AmxContext, W: torch.Tensor, b: torch.Tensor, gemm: str = "f16x3"):
         """gemm: "f16x3" (amx_rff_features_h3 on the scaled 2-limb image of W), "bf16x6"
         (amx_rff_features_x6 on the 3-limb image) or "f32"."""
@@ -662,6 +664,116 @@ class RffMap:
         phi = torch.empty(rows, self.F, dtype=torch.float32, device=c.device)
         part = torch.empty(rows // N.RFF_PART_ROWS, self.F, dtype=torch.float64, device=c.device)
         self.features(xp, rows, n, phi, part)
+        tot = torch.empty(self.F, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_sum_partials(c.h, part.data_ptr(), rows // N.RFF_PART_ROWS, self.F, tot.data_ptr(), c.stream),
+                "amx_sum_partials")
+        return phi[:n], tot
+
+
+class MlpMap:
+    """phi(x) = cos(tanh(net(x))) * sqrt(2/F), net = Linear, [ReLU, Linear]... (MLPCost.get_rep,
+    linear_cost.py:199-212, 232-237), with RffMap's interface: the hidden layers are
+    amx_gemm_bias_act_h3 launches chained through their row exponents, the last Linear runs in
+    amx_mlp_features_h3 (phi rows + fp64 column partials).  f16x3 only."""
+
+    # the hidden layers' tiles depend on the row count, so scoring one step's rows at a time
+    # rounds differently from one pass over the rollout (RolloutEngine.rollout's score_overlap)
+    step_invariant = False
+
+    def __init__(self, ctx: AmxContext, layers):
+        """`layers` = [(W, b), ...] in nn.Linear layout, the last one the feature layer.  Hidden
+        widths are zero-padded to multiples of 128 (zero weight rows and zero bias: ReLU keeps the
+        pad at 0, and the next layer's pad columns are zero)."""
+        self.ctx = ctx
+        F, D = int(layers[-1][0].shape[0]), int(layers[0][0].shape[1])
+        if round_up(F, 128) != F:
+            raise ValueError("feature_dim must be a multiple of 128 for the MFMA feature path")
+        self.F, self.D = F, D
+        self.Kp = round_up(D, 32)
+        self.gemm = "f16x3"
+        self.layers = []   # (W2, wexp, bias, out_p, k_pad) per Linear
+        k, k_pad = D, self.Kp
+        for W, b in layers:
+            out, kin = int(W.shape[0]), int(W.shape[1])
+            if kin != k or tuple(b.shape) != (out,):
+                raise ValueError(f"layer shapes {tuple(W.shape)} / {tuple(b.shape)} do not chain (expected {k} inputs)")
+            out_p = round_up(out, 128)
+            Wp = torch.zeros(out_p, k_pad, dtype=torch.float32)
+            Wp[:out, :k] = W.detach().float().cpu()
+            bp = torch.zeros(out_p, dtype=torch.float32)
+            bp[:out] = b.detach().float().cpu()
+            W2, wexp = split_f16x2(ctx, Wp.to(ctx.device).unsqueeze(0))
+            self.layers.append((W2[0], wexp[0], bp.to(ctx.device), out_p, k_pad))
+            k, k_pad = out, out_p
+        self.n_hidden = len(self.layers) - 1
+        self.h_max = max([L[3] for L in self.layers[:-1]], default=0)
+        self.W2, self.wexp = self.layers[0][0], self.layers[0][1]
+        # np.sqrt(2/F) is a float64 scalar; torch multiplies the fp32 tensor by it rounded to fp32
+        self.scale = float(np.float32(np.sqrt(2 / F)))
+        self._ws = {}
+
+    def _workspace(self, rows: int, cache: bool = True):
+        """Two ping-pong hidden buffers [rows][h_max] and the exponent slots [1 + n_hidden][rows]
+        (slot 0: the input rows, slot i + 1: hidden layer i's output rows)."""
+        ws = self._ws.get(rows)
+        if ws is None:
+            dev = self.ctx.device
+            ws = ([torch.empty(rows * self.h_max, dtype=torch.float32, device=dev) for _ in range(min(self.n_hidden, 2))],
+                  torch.empty(1 + self.n_hidden, rows, dtype=torch.int32, device=dev))
+            if cache:
+                self._ws[rows] = ws
+        return ws
+
+    def features(self, x: torch.Tensor, rows: int, n_valid: int, phi: torch.Tensor, partials: torch.Tensor,
+                 row_mask: torch.Tensor | None = None, ldx: int | None = None,
+                 row_exp: torch.Tensor | None = None, cache: bool = True) -> None:
+        """phi rows + fp64 column partials [rows / 32][F] of x's `rows` rows (RffMap.features'
+        contract).  `row_exp` [rows] int32 = the input rows' exponents (amx_step_rexp writes them
+        for the rollout's [s, s'] rows); None computes them here.  The buffers are cached per row
+        count: after the first call at a row count nothing is allocated and nothing synchronises
+        (`cache=False`: one-off buffers, for embed's arbitrary row counts)."""
+        c = self.ctx
+        if partials.dtype != torch.float64 or partials.numel() < rows // N.RFF_PART_ROWS * self.F:
+            raise ValueError(f"partials must be fp64 with room for [{rows // N.RFF_PART_ROWS}][{self.F}] "
+                             f"(one row per {N.RFF_PART_ROWS} feature rows), got {tuple(partials.shape)} "
+                             f"{partials.dtype}")
+        bufs, rexp = self._workspace(rows, cache)
+        h, ldh = x, (self.Kp if ldx is None else ldx)
+        if row_exp is None:
+            N.check(c.lib.amx_row_exponents(c.h, 1, rows, self.Kp, h.data_ptr(), ldh, 0, rexp.data_ptr(), rows, 1,
+                                            c.stream), "amx_row_exponents(mlp)")
+            row_exp = rexp[0]
+        if self.n_hidden:
+            rexp[1:].fill_(-100)   # the hidden epilogues max into their slots
+        for i, (W2, wexp, b, out_p, k_pad) in enumerate(self.layers[:-1]):
+            o = bufs[i & 1]
+            N.check(c.lib.amx_gemm_bias_act_h3(c.h, 1, rows, out_p, k_pad, h.data_ptr(), ldh, 0, W2.data_ptr(), 0,
+                                               wexp.data_ptr(), 0, b.data_ptr(), 0, o.data_ptr(), out_p, 0, 0,
+                                               N.AMX_ACT_RELU, row_exp.data_ptr(), 0, 1, rexp[i + 1].data_ptr(), 0,
+                                               c.stream), "amx_gemm_bias_act_h3(mlp)")
+            h, ldh, row_exp = o, out_p, rexp[i + 1]
+        W2, wexp, b, _, k_pad = self.layers[-1]
+        N.check(c.lib.amx_mlp_features_h3(c.h, rows, n_valid, self.F, k_pad, h.data_ptr(), ldh, W2.data_ptr(),
+                                          wexp.data_ptr(), row_exp.data_ptr(), b.data_ptr(), self.scale,
+                                          phi.data_ptr(), phi.shape[-1], partials.data_ptr(),
+                                          None if row_mask is None else row_mask.data_ptr(), c.stream),
+                "amx_mlp_features_h3")
+
+    def embed(self, x: torch.Tensor):
+        """(phi [n, F], column sums [F] fp64) of arbitrary rows x [n, D] (fp32, any device)."""
+        c = self.ctx
+        n = x.shape[0]
+        rows = round_up(max(n, 1), 128)
+        # whole rounds of the feature layer's 160 x 256 tiles where ~1 % of padding buys them
+        # (RffMap.embed), when that row count also suits the hidden layers' 128-row tiles
+        r160 = 160 * c.n_cus // max(self.F // 256, 1) if self.F % 256 == 0 else 0
+        if r160 and r160 % 128 == 0 and n >= r160 and round_up(n, r160) <= 1.05 * n:
+            rows = round_up(n, r160)
+        xp = torch.zeros(rows, self.Kp, dtype=torch.float32, device=c.device)
+        xp[:n, :self.D] = x.to(c.device, torch.float32)
+        phi = torch.empty(rows, self.F, dtype=torch.float32, device=c.device)
+        part = torch.empty(rows // N.RFF_PART_ROWS, self.F, dtype=torch.float64, device=c.device)
+        self.features(xp, rows, n, phi, part, cache=False)
         tot = torch.empty(self.F, dtype=torch.float64, device=c.device)
         N.check(c.lib.amx_sum_partials(c.h, part.data_ptr(), rows // N.RFF_PART_ROWS, self.F, tot.data_ptr(), c.stream),
                 "amx_sum_partials")

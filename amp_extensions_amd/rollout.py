@@ -416,7 +416,10 @@ class RolloutEngine:
         self._act_ready = -1
         # (the MMD features only: the GAIL discriminator's GEMMs split K differently at one step's
         # row count than over the whole rollout, which changes their fp32 rounding)
-        side = self._score_stream() if (self.score_overlap and K > 1 and isinstance(self.cost, RBFLinearCost)) else None
+        # (nor MLPCost's hidden layers, MlpMap.step_invariant: the same, and at few rows they share
+        # the context's stream-K scratch with the ensemble forward that would run beside them)
+        side = self._score_stream() if (self.score_overlap and K > 1 and isinstance(self.cost, RBFLinearCost)
+                                        and self.cost.map.step_invariant) else None
         for t in range(K):
             self.step(act_next=t + 1 < K)
             if side is not None and t + 1 < K:

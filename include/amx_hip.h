@@ -216,6 +216,16 @@ int amx_rff_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, int K, const
                         const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b, float scale,
                         float* phi, int ldphi, double* col_partials, const uint8_t* row_mask, void* stream);
 
+/* The feature layer of the MLP-feature MMD cost (MLPCost.get_rep, milo/milo/linear_cost.py:232-237:
+ * the net's last Linear, its closing Tanh, then torch.cos(.) * np.sqrt(2/F)): amx_rff_features_h3's
+ * arguments, layouts, tile dispatch and outputs (phi rows, one fp64 column partial per
+ * AMX_RFF_PART_ROWS rows over the rows below n_valid with row_mask != 0) with
+ * phi = cos(tanh(x W^T + b)) * scale, the scalar function evaluated in fp64 and rounded once.
+ * x = the last hidden layer's rows (amx_gemm_bias_act_h3 writes their exponents: row_exp_out). */
+int amx_mlp_features_h3(amx_ctx* ctx, int rows, int n_valid, int F, int K, const float* x, int ldx,
+                        const uint16_t* W2, const int* w_exp, const int* row_exp, const float* b, float scale,
+                        float* phi, int ldphi, double* col_partials, const uint8_t* row_mask, void* stream);
+
 /* SimEnv's reset noise (reset_args noise_bef_rot, noise_min, noise_max, radian, rot_vel_w_pose,
  * vel_noise, interp, knee_rot; run.py:113-117) = DeepMimicCore's cKinCharacter::AddNoise
  * (anim/KinCharacter.cpp:340-470) applied to the kinematic pose / velocity at the reset time.
