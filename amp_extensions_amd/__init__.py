@@ -18,7 +18,7 @@ __all__ = [
     "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
     "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
-    "PPO", "DevicePPO",
+    "PPO", "DevicePPO", "NPG",
 ]
 
 
@@ -44,9 +44,9 @@ def __getattr__(name):
     if name in ("DeviceMLPBaseline", "process_samples"):
         from . import gae
         return getattr(gae, name)
-    if name == "DeviceNPG":
-        from .npg import DeviceNPG
-        return DeviceNPG
+    if name in ("DeviceNPG", "NPG"):
+        from . import npg
+        return getattr(npg, name)
     if name in ("BC", "DeviceBC", "plan_bc_batches"):
         from . import bc
         return getattr(bc, name)

@@ -94,6 +94,11 @@ SIGNATURES = {
     "amx_npg_cg_xrp": (c_int, [vp, c_int, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "amx_npg_pass_cg": (c_int, [vp, c_int, vp, c_int, c_ll, vp, c_int, vp, vp, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp,
                                 vp, vp]),
+    "amx_npg_pass_idx": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_ll, vp, vp, c_int, vp, vp, vp, vp, vp]),
+    "amx_npg_pass_cg_idx": (c_int, [vp, c_int, c_int, vp, vp, c_int, c_ll, vp, c_int, vp, vp, c_dbl, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, vp, vp]),
+    "amx_npg_ll_blocks": (c_int, [vp, c_int]),
+    "amx_npg_ll": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, vp, vp, vp, vp]),
     "amx_npg_apply_step": (c_int, [vp, c_int, c_int, vp, vp, vp, c_int, c_dbl, c_dbl, c_flt, vp, vp, vp]),
     "amx_npg_pass_ex": (c_int, [vp, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, vp, c_int, vp, vp, vp, vp]),
     "amx_npg_cg_init": (c_int, [vp, c_int, vp, vp, vp, vp, vp, vp, vp]),

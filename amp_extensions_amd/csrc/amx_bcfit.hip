@@ -292,9 +292,10 @@ struct StepConsts {
 // PPO (loss_type MLE): P3 also leaves each row's sum_c z^2 as one partial per column tile in PN
 // (and, with `tracks`, that of z_old = (a - mu) / sigma_old in PO), and the step's idle waves
 // of P2 form sum log_std (and sum log_std_old).
-template <bool STEP, bool PPO = false>
+// MEAN (PPO): P3 also writes the policy mean of rows < mean_rows to mean[row][A] (amx_npg_ll).
+template <bool STEP, bool PPO = false, bool MEAN = false>
 __device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, int loss_type, const StepConsts* sc,
-                                        bool tracks = false) {
+                                        bool tracks = false, float* __restrict__ mean = nullptr, int mean_rows = 0) {
   {  // P1
     const Tid q;
     const int wave = q.wave, i = q.i, kq = q.kq;
@@ -353,6 +354,10 @@ __device__ __forceinline__ void forward(float* __restrict__ sm, const Lay& L, in
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float d = pz[r * L.AS] - (acc[r] + b);
+        if constexpr (MEAN) {
+          const int row = rt * 16 + 4 * kq + r;
+          if (mean && row < mean_rows && c < L.A) mean[(long long)row * L.A + c] = acc[r] + b;
+        }
         const float z = c < L.A ? d / sig : 0.f;
         pz[r * L.AS] = z;
         const float s = group16_sum(z * z);
@@ -815,6 +820,52 @@ __global__ __launch_bounds__(NT, 1) void k_bcfit_eval(EvalArgs a) { eval_body<fa
 
 __global__ __launch_bounds__(NT, 1) void k_ppo_old_ll(EvalArgs a, float* ll) { eval_body<true>(a, ll); }
 
+// NPG's log-likelihood pass (amx_npg_ll): k_ppo_old_ll's rows and arithmetic (the same LL bits, so
+// a ratio of equal policies is exp(0)); each workgroup also leaves the fp64 sum of its rows' LL
+// (its chunks in order, a wave butterfly per chunk) in partials[block], and, when asked, every
+// row's LL and policy mean.
+__global__ __launch_bounds__(NT, 1) void k_npg_ll(EvalArgs a, float* __restrict__ ll, float* __restrict__ mean) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const Lay L(a.S, a.A, true);
+  const Flat F(a.S, a.A);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  stage_theta(sm, L, F, a.theta);
+  __syncthreads();
+  if (wave == 0) {
+    const float sl = sum_log_std(sm + L.ls, L);
+    if (lane == 0) sm[L.SL] = sl;
+  }
+  double bsum = 0.0;
+  const int chunks = (a.N + BB - 1) / BB;
+  for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+    const int r0 = ch * BB;
+    // rows past N read row N - 1 and are left out of the sum
+#pragma unroll
+    for (int u = 0; u < XU; ++u) {
+      const int c = lane + 64 * (u & 3), r = wave * 4 + (u >> 2);
+      const int g = r0 + r < a.N ? r0 + r : a.N - 1;
+      if (c < a.S) sm[L.X + r * L.XS + c] = a.obs[(long long)g * a.ldo + c];
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int r = wave * 4 + u;
+      const int g = r0 + r < a.N ? r0 + r : a.N - 1;
+      if (lane < a.A) sm[L.ACT + r * L.AS + lane] = a.act[(long long)g * a.lda + lane];
+    }
+    __syncthreads();
+    forward<false, true, true>(sm, L, LOSS_MLE, nullptr, false, mean ? mean + (long long)r0 * a.A : nullptr,
+                               a.N - r0);
+    if (wave == 0) {
+      const bool ok = r0 + lane < a.N;
+      const float v = row_ll(sm + L.PN, sm[L.SL], L, lane);
+      if (ll && ok) ll[r0 + lane] = v;
+      bsum += amx::wave_sum(ok ? (double)v : 0.0);
+    }
+    __syncthreads();
+  }
+  if (t == 0) a.partials[blockIdx.x] = bsum;
+}
+
 // the workgroups' partials in workgroup order -> mean((mu - a)^2) or -mean(LL)
 __global__ void k_bcfit_eval_sum(const double* __restrict__ partials, int nb, int N, int A, int loss_type,
                                  double* __restrict__ out) {
@@ -958,6 +1009,39 @@ extern "C" int amx_ppo_old_ll(amx_ctx* ctx, int N, const float* obs, long long l
   if (nb > chunks) nb = chunks;
   EvalArgs a = {ctx->S, ctx->A, N, LOSS_MLE, obs, ldo, act, lda, theta, nullptr};
   hipLaunchKernelGGL(k_ppo_old_ll, dim3(nb), dim3(NT), L.bytes(), (hipStream_t)stream, a, ll_old);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+// ---- NPG's log-likelihood pass (the BC term of NPG.CPI_surrogate and its dist-info entries) ------
+
+namespace {
+int npg_ll_blocks(const amx_ctx* ctx, int N) {
+  const int chunks = (N + BB - 1) / BB;
+  int nb = ctx->n_cus > 0 ? ctx->n_cus : 1;
+  if (nb > EVAL_MAXB) nb = EVAL_MAXB;
+  return nb > chunks ? chunks : nb;
+}
+}  // namespace
+
+extern "C" int amx_npg_ll_blocks(amx_ctx* ctx, int N) {
+  if (!ctx || N <= 0) return -1;
+  return npg_ll_blocks(ctx, N);
+}
+
+extern "C" int amx_npg_ll(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+                          const float* theta, double* partials, float* ll, float* mean, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_npg_ll: null ctx");
+  int rc = check_data("amx_npg_ll", ctx, N, obs, ldo, act, lda, LOSS_MLE);
+  if (rc) return rc;
+  AMX_CHECK_ARG(theta && partials, "amx_npg_ll: null theta / partials");
+  AMX_CHECK_ARG(((uintptr_t)partials & 7u) == 0, "amx_npg_ll: misaligned partials");
+  const Lay L(ctx->S, ctx->A, true);
+  AMX_CHECK_ARG(L.bytes() <= 160 * 1024, "amx_npg_ll: %zu B of LDS", L.bytes());
+  rc = allow_lds(k_npg_ll, L.bytes());
+  if (rc) return rc;
+  EvalArgs a = {ctx->S, ctx->A, N, LOSS_MLE, obs, ldo, act, lda, theta, partials};
+  hipLaunchKernelGGL(k_npg_ll, dim3(npg_ll_blocks(ctx, N)), dim3(NT), L.bytes(), (hipStream_t)stream, a, ll, mean);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
 }

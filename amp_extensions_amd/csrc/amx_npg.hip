@@ -105,8 +105,13 @@ struct NpgArgs {
   int mode, N, S, A;
   int rows_per_block;
   const void* obs; long long ldo;
-  const void* act; long long lda;
-  const double* adv;         // VPG / EVAL (whitened advantages)
+  // FVP reads neither actions nor advantages: the IDX kernels (amx_npg_pass_idx /
+  // amx_npg_pass_cg_idx) take their two operands in those slots, so the argument block keeps its
+  // size and every other kernel its code.  The pass runs over the N rows obs[row_idx[k]] (and
+  // hcache[row_idx[k]]); prod_count (optional) counts the products taken.
+  union { const void* act; const int* row_idx; };
+  long long lda;
+  union { const double* adv; double* prod_count; };  // adv: VPG / EVAL (whitened advantages)
   const float* theta;        // packed parameters (old, for EVAL)
   const float* vec;          // FVP: tangent; EVAL: new parameters
   double* partials;          // VPG/FVP: [blocks][P]; EVAL: [blocks][2]
@@ -293,8 +298,11 @@ __device__ __forceinline__ pf4 mma(float a, float b, pf4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int MODE, typename TO, typename TA, int RC, int JJM, bool HC = false>
+template <int MODE, typename TO, typename TA, int RC, int JJM, bool HC = false, bool IDX = false>
 __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
+  // IDX (FVP): chunk row k of the pass is the observation (and cached) row a.row_idx[k]: a
+  // subsampled Fisher (NPG.HVP with hvp_sample_frac < 1, npg_cg.py:90-94); duplicates are legal
+  static_assert(!IDX || MODE == NPG_FVP, "the index vector serves the Fisher-vector pass only");
   // JJM: layer-1 K steps compiled (>= ceil(S / 16); steps past S multiply zero weights)
   // HC (FVP): the theta forward (H1, H2) is read from a.hcache, written by the VPG pass of the
   // same update (same kernels, same bits), instead of recomputed: layer 1 computes only the
@@ -340,6 +348,9 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
       if (!cg_fold(a, X, t)) return;
       fold = true;
     }
+  }
+  if constexpr (IDX) {  // a product is taken: the caller's count of the solve's products
+    if (a.prod_count && blockIdx.x == 0 && t == 0) a.prod_count[0] += 1.0;
   }
   // Setup issues every global load before the first store (one memory round trip, not one per
   // array): W1 (and the tangent's / new W1) as coalesced float4s, the small parameter images,
@@ -393,7 +404,10 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
   constexpr bool need_act = mode != NPG_FVP;
   auto prefetch = [&](int c0, int nr) {
     const bool rv = pr < nr;
-    const TO* xs = static_cast<const TO*>(a.obs) + (long long)(c0 + (rv ? pr : 0)) * a.ldo + pc;
+    long long xrow;
+    if constexpr (IDX) xrow = rv ? a.row_idx[c0 + pr] : 0;
+    else xrow = (long long)(c0 + (rv ? pr : 0));
+    const TO* xs = static_cast<const TO*>(a.obs) + xrow * a.ldo + pc;
 #pragma unroll
     for (int u = 0; u < XU; ++u) xv[u] = (rv && pc + TPR * u < S) ? xs[TPR * u] : TO(0);
     if (need_act) {
@@ -404,7 +418,9 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
     }
     if (HCF) {
       const int hr = t >> 4;
-      hv = (t < RC * 16 && hr < nr) ? *reinterpret_cast<const pf4*>(a.hcache + (long long)(c0 + hr) * HCW + 4 * (t & 15))
+      int hrow = c0 + hr;
+      if constexpr (IDX) hrow = (t < RC * 16 && hr < nr) ? a.row_idx[c0 + hr] : 0;
+      hv = (t < RC * 16 && hr < nr) ? *reinterpret_cast<const pf4*>(a.hcache + (long long)hrow * HCW + 4 * (t & 15))
                                      : pf4{0.f, 0.f, 0.f, 0.f};
     }
   };
@@ -1273,7 +1289,7 @@ namespace {
 int npg_launch(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, long long ldo, const void* act,
                int act_dtype, long long lda, const double* adv, const float* theta, const float* vec,
                int rows_per_block, double* partials, const double* gate, float* hcache, const NpgArgs* cg,
-               void* stream) {
+               void* stream, const int* row_idx = nullptr, double* prod_count = nullptr) {
   const int S = ctx->S, A = ctx->A;
   NpgArgs a = {};
   if (cg) a = *cg;
@@ -1282,6 +1298,10 @@ int npg_launch(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, lo
   a.act = act; a.lda = lda;
   a.adv = adv; a.theta = theta; a.vec = vec; a.partials = partials; a.gate = gate; a.hcache = hcache;
   a.P = (int)amx_npg_param_count(S, A);
+  if (row_idx) {
+    a.row_idx = row_idx;
+    a.prod_count = prod_count;
+  }
   const bool of64 = obs_dtype == AMX_IN_F64, af64 = act_dtype == AMX_IN_F64;
   AMX_CHECK_ARG(!hcache || mode == NPG_VPG || (mode == NPG_FVP && !of64),
                 "amx_npg_pass: hcache is written by VPG and read by FVP on fp32 observations (mode %d)", mode);
@@ -1293,7 +1313,15 @@ int npg_launch(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, lo
   // ceil(S / 16) rounded up to 4, 8, 13 or 16 steps; fp64 inputs the 16-step kernel
   const int jj = (S + 15) / 16;
   void (*kern)(NpgArgs) = nullptr;
-  if (!of64 && (mode == NPG_FVP || !af64)) {
+  if (row_idx) {  // fp32 observations, FVP (checked by the entry points)
+#define NPG_PICK(J) \
+  kern = hcache ? k_npg<NPG_FVP, float, float, RC0, J, true, true> : k_npg<NPG_FVP, float, float, RC0, J, false, true>
+    if (jj <= 4) NPG_PICK(4);
+    else if (jj <= 8) NPG_PICK(8);
+    else if (jj <= 13) NPG_PICK(13);
+    else NPG_PICK(16);
+#undef NPG_PICK
+  } else if (!of64 && (mode == NPG_FVP || !af64)) {
 #define NPG_PICK(J)                                                                                  \
   kern = mode == NPG_FVP ? (hcache ? k_npg<NPG_FVP, float, float, RC0, J, true> : k_npg<NPG_FVP, float, float, RC0, J>) \
        : mode == NPG_VPG ? k_npg<NPG_VPG, float, float, RC0, J> : k_npg<NPG_EVAL, float, float, RC0, J>
@@ -1338,6 +1366,28 @@ extern "C" int amx_npg_pass_ex(amx_ctx* ctx, int mode, int N, const void* obs, i
                     gate, hcache, nullptr, stream);
 }
 
+namespace {
+// the fold's operands (amx_npg_pass_cg / amx_npg_pass_cg_idx): checked, then packed into cg
+int npg_fold_args(const char* fn, amx_ctx* ctx, double tol, double* x, const double* r_in, double* r_out,
+                  const double* p_in, double* p_out, float* p32_out, const double* state_in, double* state_out,
+                  const double* work, NpgArgs* cg) {
+  const int S = ctx->S, A = ctx->A;
+  AMX_CHECK_ARG(x && r_in && r_out && p_in && p_out && p32_out && state_in && state_out && work, "%s: null buffer", fn);
+  AMX_CHECK_ARG(r_in != r_out && p_in != p_out && state_in != state_out,
+                "%s: r, p and the state must alternate buffers (every block reads all of them)", fn);
+  const int P = (int)amx_npg_param_count(S, A);
+  const Geo g(S, A);
+  // p' (P floats) and the 16 wave sums are staged from the X tile to the end of the LDS image
+  const size_t region = npg_lds_bytes(S, A, NPG_FVP, RC0) - sizeof(float) * 2 * small_floats(g);
+  AMX_CHECK_ARG(P <= NT * 2 * CGE && sizeof(float) * (r4(P) + 4 * NW) <= region,
+                "%s: P=%d does not fit the fold (<= %d, %zu B of staging)", fn, P, NT * 2 * CGE, region);
+  cg->cg_state_in = state_in; cg->cg_state_out = state_out; cg->cg_tol = tol;
+  cg->cg_x = x; cg->cg_r_in = r_in; cg->cg_r_out = r_out;
+  cg->cg_p_in = p_in; cg->cg_p_out = p_out; cg->cg_p32_out = p32_out; cg->cg_work = work;
+  return AMX_OK;
+}
+}  // namespace
+
 extern "C" int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dtype, long long ldo,
                                const float* theta, int rows_per_block, double* partials, float* hcache, double tol,
                                double* x, const double* r_in, double* r_out, const double* p_in, double* p_out,
@@ -1349,24 +1399,58 @@ extern "C" int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dty
                 A, MAXA);
   AMX_CHECK_ARG(N > 0 && rows_per_block > 0 && rows_per_block % RC0 == 0,
                 "amx_npg_pass_cg: N=%d rows_per_block=%d (multiple of %d)", N, rows_per_block, RC0);
-  AMX_CHECK_ARG(obs && theta && partials && x && r_in && r_out && p_in && p_out && p32_out && state_in && state_out &&
-                    work,
-                "amx_npg_pass_cg: null buffer");
-  AMX_CHECK_ARG(r_in != r_out && p_in != p_out && state_in != state_out,
-                "amx_npg_pass_cg: r, p and the state must alternate buffers (every block reads all of them)");
+  AMX_CHECK_ARG(obs && theta && partials, "amx_npg_pass_cg: null buffer");
   AMX_CHECK_ARG(ldo >= S && ((uintptr_t)theta & 15) == 0, "amx_npg_pass_cg: ldo=%lld, theta 16-byte aligned", ldo);
-  const int P = (int)amx_npg_param_count(S, A);
-  const Geo g(S, A);
-  // p' (P floats) and the 16 wave sums are staged from the X tile to the end of the LDS image
-  const size_t region = npg_lds_bytes(S, A, NPG_FVP, RC0) - sizeof(float) * 2 * small_floats(g);
-  AMX_CHECK_ARG(P <= NT * 2 * CGE && sizeof(float) * (r4(P) + 4 * NW) <= region,
-                "amx_npg_pass_cg: P=%d does not fit the fold (<= %d, %zu B of staging)", P, NT * 2 * CGE, region);
   NpgArgs cg = {};
-  cg.cg_state_in = state_in; cg.cg_state_out = state_out; cg.cg_tol = tol;
-  cg.cg_x = x; cg.cg_r_in = r_in; cg.cg_r_out = r_out;
-  cg.cg_p_in = p_in; cg.cg_p_out = p_out; cg.cg_p32_out = p32_out; cg.cg_work = work;
+  int rc = npg_fold_args("amx_npg_pass_cg", ctx, tol, x, r_in, r_out, p_in, p_out, p32_out, state_in, state_out, work,
+                         &cg);
+  if (rc) return rc;
   return npg_launch(ctx, NPG_FVP, N, obs, obs_dtype, ldo, obs, AMX_IN_F32, A, nullptr, theta, nullptr,
                     rows_per_block, partials, nullptr, hcache, &cg, stream);
+}
+
+namespace {
+int npg_idx_checks(const char* fn, amx_ctx* ctx, int N, int M, const int32_t* row_idx, const void* obs, int obs_dtype,
+                   long long ldo, const float* theta, int rows_per_block, double* partials, float* hcache) {
+  AMX_CHECK_ARG(ctx, "%s: null ctx", fn);
+  const int S = ctx->S, A = ctx->A;
+  AMX_CHECK_ARG(S > 0 && S <= MAXS && A > 0 && A <= MAXA, "%s: S=%d (<= %d), A=%d (<= %d)", fn, S, MAXS, A, MAXA);
+  AMX_CHECK_ARG(N > 0 && M > 0 && rows_per_block > 0 && rows_per_block % RC0 == 0,
+                "%s: N=%d M=%d rows_per_block=%d (multiple of %d)", fn, N, M, rows_per_block, RC0);
+  AMX_CHECK_ARG(obs_dtype == AMX_IN_F32, "%s: the indexed pass reads fp32 observations (obs_dtype=%d)", fn, obs_dtype);
+  AMX_CHECK_ARG(row_idx && obs && theta && partials, "%s: null buffer", fn);
+  AMX_CHECK_ARG(ldo >= S && ((uintptr_t)theta & 15) == 0 && ((uintptr_t)hcache & 15) == 0,
+                "%s: ldo=%lld; theta / hcache 16-byte aligned", fn, ldo);
+  return AMX_OK;
+}
+}  // namespace
+
+extern "C" int amx_npg_pass_idx(amx_ctx* ctx, int N, int M, const int32_t* row_idx, const void* obs, int obs_dtype,
+                                long long ldo, const float* theta, const float* vec, int rows_per_block,
+                                double* partials, const double* gate, float* hcache, double* prod_count,
+                                void* stream) {
+  int rc = npg_idx_checks("amx_npg_pass_idx", ctx, N, M, row_idx, obs, obs_dtype, ldo, theta, rows_per_block, partials,
+                          hcache);
+  if (rc) return rc;
+  AMX_CHECK_ARG(vec && ((uintptr_t)vec & 15) == 0, "amx_npg_pass_idx: vec null or not 16-byte aligned");
+  return npg_launch(ctx, NPG_FVP, M, obs, obs_dtype, ldo, obs, AMX_IN_F32, ctx->A, nullptr, theta, vec,
+                    rows_per_block, partials, gate, hcache, nullptr, stream, row_idx, prod_count);
+}
+
+extern "C" int amx_npg_pass_cg_idx(amx_ctx* ctx, int N, int M, const int32_t* row_idx, const void* obs, int obs_dtype,
+                                   long long ldo, const float* theta, int rows_per_block, double* partials,
+                                   float* hcache, double tol, double* x, const double* r_in, double* r_out,
+                                   const double* p_in, double* p_out, float* p32_out, const double* state_in,
+                                   double* state_out, const double* work, double* prod_count, void* stream) {
+  int rc = npg_idx_checks("amx_npg_pass_cg_idx", ctx, N, M, row_idx, obs, obs_dtype, ldo, theta, rows_per_block,
+                          partials, hcache);
+  if (rc) return rc;
+  NpgArgs cg = {};
+  rc = npg_fold_args("amx_npg_pass_cg_idx", ctx, tol, x, r_in, r_out, p_in, p_out, p32_out, state_in, state_out, work,
+                     &cg);
+  if (rc) return rc;
+  return npg_launch(ctx, NPG_FVP, M, obs, obs_dtype, ldo, obs, AMX_IN_F32, ctx->A, nullptr, theta, nullptr,
+                    rows_per_block, partials, nullptr, hcache, &cg, stream, row_idx, prod_count);
 }
 
 extern "C" int amx_npg_reduce(amx_ctx* ctx, const double* partials, int blocks, int P, double* out, void* stream) {

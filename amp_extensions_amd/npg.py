@@ -8,13 +8,21 @@ device between passes.  Parameters live in the reference's flat order (MLP.train
 W1, b1, W2, b2, W3, b3, log_std — gaussian_mlp.py:44-62), so `get_param_values` /
 `set_param_values` exchange the same vectors as the reference policy.
 
-Same semantics as the reference with hvp_sample_frac = 1 (MILO's default,
-milo/milo/arguments.py:122) and no input normalization (FCNetwork's default in_shift/in_scale:
-(x - 0) / (1 + 1e-8) == x in float32); a subsampled FIM or input normalization raise.
+Same semantics as the reference without input normalization (FCNetwork's default
+in_shift/in_scale: (x - 0) / (1 + 1e-8) == x in float32); input normalization raises.  A
+subsampled Fisher (hvp_sample_frac < 1, npg_cg.py:90-94) runs the Fisher-vector pass over an index
+vector (amx_npg_pass_idx), one vector per CG iteration drawn from numpy's global generator as the
+reference draws them; the BC term of NPG.CPI_surrogate (npg_cg.py:79-84) is one more VPG pass over
+the expert rows with every advantage equal to reg_coeff, and a log-likelihood pass (amx_npg_ll) for
+the surrogate's values.
+
+`NPG` is the drop-in (the reference's constructor, `train_from_paths(paths, infos)`, `logger`,
+`running_score`), built like ppo.PPO: `class NPG(amx.NPG, BatchREINFORCE): pass`.
 """
 from __future__ import annotations
 
 import math
+import time as timer
 
 import numpy as np
 import torch
@@ -59,8 +67,6 @@ class DeviceNPG:
     def __init__(self, ctx: AmxContext, policy_layers, log_std, normalized_step_size=0.01, const_learn_rate=None,
                  FIM_invert_args=None, hvp_sample_frac=1.0, kl_dist=None, min_log_std=-3.0,
                  input_normalization=None, policy=None, residual_tol=1e-10):
-        if hvp_sample_frac is not None and hvp_sample_frac < 0.99:
-            raise NotImplementedError("subsampled Fisher (hvp_sample_frac < 1) is not implemented")
         if input_normalization:
             raise NotImplementedError("running input normalization is not implemented")
         if len(policy_layers) != 3 or any(W.shape[0] != 32 for W, _ in policy_layers[:2]):
@@ -78,6 +84,11 @@ class DeviceNPG:
         self.min_log_std = float(min_log_std)
         self.residual_tol = residual_tol
         self.policy = policy
+        self.hvp_subsample = hvp_sample_frac  # < 0.99: the Fisher on int(frac * N) rows drawn per CG iteration
+        self.bc = None            # (expert_obs, expert_act, reg_coeff): the BC term of CPI_surrogate
+        self.dist_info = False    # return old_dist_info / new_dist_info / lr
+        self.eval_before = False  # compute surr_before (always with a BC term)
+        self.hvp_products = 0     # Fisher-vector products the last subsampled solve took
         self.P = int(ctx.lib.amx_npg_param_count(self.S, self.A))
         self.theta = torch.from_numpy(pack_policy(policy_layers, log_std)).to(ctx.device)
         assert self.theta.numel() == self.P
@@ -116,17 +127,21 @@ class DeviceNPG:
         # one block per CU (the pass kernel holds ~140 KB of LDS): one wave of blocks
         return max(32, int(math.ceil(n / 256 / 32)) * 32)
 
-    def _pass(self, mode, obs, act, adv, vec, gate=None, hcache=None, reduce=True, out=None):
+    def _pass(self, mode, obs, act, adv, vec, gate=None, hcache=None, reduce=True, out=None, part=None):
         """One pass (amx_npg_pass_ex) and its block-order reduction (into `out` when given);
         reduce=False returns the [blocks][width] partials instead (the CG folds their reduction
-        into its step)."""
+        into its step).  `part`: the rows of a larger partials buffer to write (no reduction)."""
         c = self.ctx
         n = obs.shape[0]
         rpb = self._rows_per_block(n)
         nb = (n + rpb - 1) // rpb
         width = 2 if mode == NPG_EVAL else self.P
         key = (nb, width)
-        part = self._bufs.get(key)
+        if part is not None:
+            assert part.shape == (nb, width) and part.is_contiguous()
+            reduce = False
+        else:
+            part = self._bufs.get(key)
         if part is None:
             part = self._bufs[key] = torch.empty(nb, width, dtype=torch.float64, device=c.device)
         od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
@@ -162,10 +177,82 @@ class DeviceNPG:
                 raise ValueError("advantages must have one entry per observation")
         return obs, act, adv
 
-    def flat_vpg(self, observations, actions, advantages) -> torch.Tensor:
+    def _pass_idx(self, obs, idx, vec, gate=None, hcache=None, count=None):
+        """The Fisher-vector pass over the rows obs[idx] (amx_npg_pass_idx; idx: device int32 [M],
+        0 <= idx < N): the [blocks][P] partials of the plain pass on the materialised rows."""
+        c = self.ctx
+        m = idx.numel()
+        if obs.dtype != torch.float32 or idx.dtype != torch.int32 or not idx.is_contiguous() or m == 0:
+            raise ValueError("the indexed pass takes fp32 observations and a non-empty contiguous int32 index vector")
+        rpb = self._rows_per_block(m)
+        nb = (m + rpb - 1) // rpb
+        part = self._bufs.get((nb, self.P))
+        if part is None:
+            part = self._bufs[(nb, self.P)] = torch.empty(nb, self.P, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_npg_pass_idx(c.h, obs.shape[0], m, idx.data_ptr(), obs.data_ptr(), N.AMX_IN_F32,
+                                       obs.stride(0), self.theta.data_ptr(), vec.data_ptr(), rpb, part.data_ptr(),
+                                       N.ptr(gate), N.ptr(hcache), N.ptr(count), c.stream), "amx_npg_pass_idx")
+        return part
+
+    def _index_table(self, idx, n: int):
+        """Host or device row indices -> a contiguous device int32 tensor, range-checked on the
+        host when they come from there (the kernels trust 0 <= idx < N)."""
+        if isinstance(idx, torch.Tensor) and idx.is_cuda:
+            return idx.to(torch.int32).contiguous()
+        a = np.ascontiguousarray(np.asarray(idx), dtype=np.int32)
+        if a.size == 0 or a.min() < 0 or a.max() >= n:
+            raise ValueError(f"row indices must be a non-empty set in [0, {n})")
+        return torch.from_numpy(a).to(self.ctx.device)
+
+    def log_likelihood(self, obs, act, theta=None, rows=False, out=None):
+        """sum_r LL_r of the rows at `theta` (default: the current parameters) as a device fp64
+        scalar in out[0] (amx_npg_ll's block partials, summed in block order); rows=True also
+        returns every row's LL (fp32 [N]) and policy mean (fp32 [N][A])."""
+        c = self.ctx
+        n = obs.shape[0]
+        theta = self.theta if theta is None else theta
+        nb = int(c.lib.amx_npg_ll_blocks(c.h, n))
+        part = torch.empty(nb, dtype=torch.float64, device=c.device)
+        ll = torch.empty(n, dtype=torch.float32, device=c.device) if rows else None
+        mean = torch.empty(n, self.A, dtype=torch.float32, device=c.device) if rows else None
+        N.check(c.lib.amx_npg_ll(c.h, n, obs.data_ptr(), obs.stride(0), act.data_ptr(), act.stride(0),
+                                 theta.data_ptr(), part.data_ptr(), N.ptr(ll), N.ptr(mean), c.stream), "amx_npg_ll")
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), nb, 1, out.data_ptr(), None, c.stream),
+                "amx_npg_reduce")
+        return (out, ll, mean) if rows else out
+
+    def _vpg(self, obs, act, adv, hcache=None, bc=None) -> torch.Tensor:
+        """The gradient of CPI_surrogate at new == old.  With a BC term: the rollout's VPG partials
+        and those of the expert rows with every advantage equal to reg_coeff (the pass divides by
+        its own N: reg_coeff * mean(LL)'s gradient) in one buffer, summed by one reduction, the
+        rollout's blocks first."""
+        if bc is None:
+            return self._pass(NPG_VPG, obs, act, adv, None, hcache=hcache)
+        c = self.ctx
+        eo, ea, reg = bc
+        nb, nbe = (math.ceil(x.shape[0] / self._rows_per_block(x.shape[0])) for x in (obs, eo))
+        part = torch.empty(nb + nbe, self.P, dtype=torch.float64, device=c.device)
+        self._pass(NPG_VPG, obs, act, adv, None, hcache=hcache, part=part[:nb])
+        eadv = torch.full((eo.shape[0],), float(reg), dtype=torch.float64, device=c.device)
+        self._pass(NPG_VPG, eo, ea, eadv, None, part=part[nb:])
+        out = torch.empty(self.P, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), nb + nbe, self.P, out.data_ptr(), None, c.stream),
+                "amx_npg_reduce")
+        return out
+
+    def _bc_inputs(self, bc):
+        if bc is None:
+            return None
+        eo, ea, reg = bc
+        eo, ea, _ = self._inputs(eo, ea)
+        return eo, ea, float(reg)
+
+    def flat_vpg(self, observations, actions, advantages, bc=None) -> torch.Tensor:
         """BatchREINFORCE.flat_vpg (batch_reinforce.py:58-62) at new == old: fp64 [P]."""
         obs, act, adv = self._inputs(observations, actions, advantages)
-        return self._pass(NPG_VPG, obs, act, adv, None)
+        return self._vpg(obs, act, adv, bc=self._bc_inputs(bc))
 
     def _ls_curvature(self) -> torch.Tensor:
         """d^2 mean_kl / d log_std^2 at new == old (gaussian_mlp.py:144-155 with Dr's 1e-8):
@@ -176,15 +263,24 @@ class DeviceNPG:
                 "amx_npg_curvature")
         return curv
 
-    def HVP(self, observations, actions, vector, regu_coef=None) -> torch.Tensor:
-        """NPG.HVP (npg_cg.py:87-106): Fisher (mean_kl Hessian) times `vector` + damping."""
+    def HVP(self, observations, actions, vector, regu_coef=None, idx=None) -> torch.Tensor:
+        """NPG.HVP (npg_cg.py:87-106): Fisher (mean_kl Hessian) times `vector` + damping.  `idx`:
+        the rows of the subsampled Fisher (the reference's rand_idx)."""
         obs, act, _ = self._inputs(observations, actions)
-        return self._hvp(obs, act, torch.as_tensor(vector).to(self.ctx.device), regu_coef)
+        if idx is not None:
+            idx = self._index_table(idx, obs.shape[0]).reshape(-1)
+        return self._hvp(obs, act, torch.as_tensor(vector).to(self.ctx.device), regu_coef, idx)
 
-    def _hvp(self, obs, act, v, regu_coef=None):
+    def _hvp(self, obs, act, v, regu_coef=None, idx=None):
         regu = self.damping if regu_coef is None else regu_coef
         v32 = v.to(torch.float32).contiguous()   # the reference casts the vector to float32
-        h = self._pass(NPG_FVP, obs, act, None, v32)
+        if idx is None:
+            h = self._pass(NPG_FVP, obs, act, None, v32)
+        else:
+            part = self._pass_idx(obs, idx, v32)
+            h = torch.empty(self.P, dtype=torch.float64, device=self.ctx.device)
+            N.check(self.ctx.lib.amx_npg_reduce_gated(self.ctx.h, part.data_ptr(), part.shape[0], self.P,
+                                                      h.data_ptr(), None, self.ctx.stream), "amx_npg_reduce")
         h[-self.A:] += self._ls_curvature() * v32[-self.A:].double()
         return h + regu * v.to(torch.float64)  # hvp_flat + regu_coef * vector (npg_cg.py:105: the fp64 vector)
 
@@ -196,7 +292,7 @@ class DeviceNPG:
             hc = self._bufs["hcache"] = torch.empty(n, 64, dtype=torch.float32, device=self.ctx.device)
         return hc
 
-    def cg_solve(self, obs, act, b: torch.Tensor, hcache=None) -> torch.Tensor:
+    def cg_solve(self, obs, act, b: torch.Tensor, hcache=None, idx=None, count=None) -> torch.Tensor:
         """mjrl/mjrl/utils/cg_solve.py:3-23 (starts from zeros; stops at rdotr < tol) with
         NPG.HVP as the operator.  Each iteration is one Fisher-vector pass and one column-sum
         launch (amx_npg_cg_reduce: z and the p.z parts per block); the vector step (x, r, p from
@@ -207,11 +303,19 @@ class DeviceNPG:
         device-side `live` flag (a finished solve leaves x unchanged), so no host sync between
         iterations; after the stop the passes and reductions are empty launches.  `hcache`: the
         theta forward written by this update's VPG pass (train_from_arrays), so every product
-        skips layers 1-2 at theta (bit-identical products)."""
+        skips layers 1-2 at theta (bit-identical products).  `idx`: a device int32 [iters][M]
+        table, iteration i's product on the rows obs[idx[i]] (NPG.HVP's subsampled Fisher, one
+        draw per product); `count` (device fp64 [1], zeroed by the caller) then counts the
+        products taken, i.e. the draws the reference's loop makes before its break."""
         c = self.ctx
         P = self.P
         dev = c.device
         b = b.to(torch.float64).contiguous()
+        if idx is not None:
+            if idx.dim() != 2 or idx.shape[0] < self.cg_iters or idx.dtype != torch.int32 or not idx.is_contiguous():
+                raise ValueError("idx must be a contiguous int32 [cg_iters][M] device table")
+            if obs.dtype != torch.float32:
+                raise ValueError("the subsampled Fisher takes fp32 observations")
         x, r, p, r2, p2 = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(5))
         p32, p32b = (torch.empty(P, dtype=torch.float32, device=dev) for _ in range(2))
         state, state2 = (torch.empty(2, dtype=torch.float64, device=dev) for _ in range(2))
@@ -225,8 +329,11 @@ class DeviceNPG:
                                                        device=dev)
         hc = hcache if obs.dtype == torch.float32 else None
         if not self.cg_fold:
-            for _ in range(self.cg_iters):
-                part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False)
+            for it in range(self.cg_iters):
+                if idx is None:
+                    part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False)
+                else:
+                    part = self._pass_idx(obs, idx[it], p32, gate=state, hcache=hc, count=count)
                 # the partials' column sums and the vector step (amx_npg_cg_tail: two launches); r
                 # and the state alternate buffers from one iteration to the next
                 N.check(c.lib.amx_npg_cg_tail(c.h, part.data_ptr(), part.shape[0], P, self.A, curv.data_ptr(),
@@ -237,11 +344,21 @@ class DeviceNPG:
                 state, state2 = state2, state
             return x
         n = obs.shape[0]
-        rpb = self._rows_per_block(n)
+        rpb = self._rows_per_block(n if idx is None else idx.shape[1])
         od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
         for it in range(self.cg_iters):
-            if it == 0:
+            if it == 0 and idx is None:
                 part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False)
+            elif it == 0:
+                part = self._pass_idx(obs, idx[0], p32, gate=state, hcache=hc, count=count)
+            elif idx is not None:
+                N.check(c.lib.amx_npg_pass_cg_idx(c.h, n, idx.shape[1], idx[it].data_ptr(), obs.data_ptr(), od,
+                                                  obs.stride(0), self.theta.data_ptr(), rpb, part.data_ptr(),
+                                                  N.ptr(hc), self.residual_tol, x.data_ptr(), r.data_ptr(),
+                                                  r2.data_ptr(), p.data_ptr(), p2.data_ptr(), p32b.data_ptr(),
+                                                  state.data_ptr(), state2.data_ptr(), work.data_ptr(), N.ptr(count),
+                                                  c.stream), "amx_npg_pass_cg_idx")
+                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
             else:
                 # the previous iteration's vector step, then the product with its p'; r, p, p32
                 # and the state alternate buffers (every block reads all of them)
@@ -267,10 +384,37 @@ class DeviceNPG:
         return float(tot[0]) / n, float(tot[1]) / n
 
     # ---- the update ------------------------------------------------------------------------
-    def train_from_arrays(self, observations, actions, advantages, whiten: bool = True) -> dict:
+    def draw_hvp_rows(self, n: int):
+        """The reference's draws for one solve (NPG.HVP, npg_cg.py:90-92): cg_iters vectors of
+        int(frac * n) rows from numpy's global generator, in its order.  Returns the int32
+        [iters][M] table and the generator's state after 0, 1, ... iters draws."""
+        m = int(self.hvp_subsample * n)
+        if m < 1:
+            raise ValueError(f"hvp_sample_frac {self.hvp_subsample} leaves no row of {n}")
+        states, rows = [np.random.get_state()], []
+        for _ in range(self.cg_iters):
+            rows.append(np.random.choice(n, size=m))
+            states.append(np.random.get_state())
+        return np.asarray(rows, dtype=np.int32).reshape(self.cg_iters, m), states
+
+    def train_from_arrays(self, observations, actions, advantages, whiten: bool = True, bc=None,
+                          dist_info=None, idx=None) -> dict:
         """NPG.train_from_paths on concatenated arrays (npg_cg.py:113-199): whitening
         (batch_reinforce.py:284-285), VPG, CG, step size, update with the log_std clamp,
-        surr_after and kl_dist.  Returns the reference's infos entries."""
+        surr_after and kl_dist.  Returns the reference's infos entries.
+
+        `bc` (default self.bc): (expert_obs, expert_act, reg_coeff), the BC term of CPI_surrogate
+        in the gradient, surr_before and surr_after.  `dist_info` (default self.dist_info): also
+        old_dist_info / new_dist_info ([LL, mean, log_std]) and lr of the new parameters against
+        the old, where the reference's last CPI_surrogate call takes them.  `idx`: the
+        [cg_iters][M] rows of the subsampled Fisher; by default, with hvp_sample_frac < 0.99, they
+        are drawn as the reference draws them and numpy's generator is left after as many draws
+        as the solve took products.  With none of these the update is the plain one."""
+        bc = self.bc if bc is None else bc
+        dist_info = self.dist_info if dist_info is None else dist_info
+        sub = idx is not None or (self.hvp_subsample is not None and self.hvp_subsample < 0.99)
+        if bc is not None or dist_info or sub or self.eval_before:
+            return self._train_ext(observations, actions, advantages, whiten, bc, dist_info, idx, sub)
         obs, act, adv = self._inputs(observations, actions, advantages)
         c = self.ctx
         n = obs.shape[0]
@@ -303,6 +447,66 @@ class DeviceNPG:
         return {"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h, "surr_before": 0.0,
                 "surr_after": surr_h / n, "kl_dist": kl_h / n, "advantages": adv}
 
+    def _train_ext(self, observations, actions, advantages, whiten, bc, dist_info, idx, sub) -> dict:
+        """train_from_arrays with a BC term, a subsampled Fisher, the dist-info entries or a
+        computed surr_before: the same launches in the same order, plus theirs."""
+        obs, act, adv = self._inputs(observations, actions, advantages)
+        c, dev = self.ctx, self.ctx.device
+        n = obs.shape[0]
+        bc = self._bc_inputs(bc)
+        states = None
+        if sub and self.cg_iters > 0:
+            if idx is None:
+                idx, states = self.draw_hvp_rows(n)
+            idx = self._index_table(idx, n)
+            if idx.dim() != 2 or idx.shape[0] < self.cg_iters:
+                raise ValueError(f"idx must hold {self.cg_iters} index vectors")
+        else:
+            idx = None
+        if whiten:
+            w = torch.empty_like(adv)
+            stats = torch.empty(2, dtype=torch.float64, device=dev)
+            N.check(c.lib.amx_adv_whiten(c.h, 1, n, None, None, n, adv.data_ptr(), 1e-6, w.data_ptr(),
+                                         stats.data_ptr(), c.stream), "amx_adv_whiten")
+            adv = w
+        # [alpha, n_step_size, gdot | surr_after, kl | surr_before, kl_before | products |
+        #  sum LL(expert) at the old, at the new parameters]: one buffer, read back in one copy
+        res = torch.zeros(10, dtype=torch.float64, device=dev)
+        old = self.theta
+        hc = self._hcache(n)
+        vpg = self._vpg(obs, act, adv, hcache=hc, bc=bc)
+        self._pass(NPG_EVAL, obs, act, adv, old, out=res[5:7])  # new == old: LR == 1 on every row
+        if bc is not None:
+            self.log_likelihood(bc[0], bc[1], old, out=res[8:9])
+        npg = self.cg_solve(obs, act, vpg, hcache=hc, idx=idx, count=res[7:8])
+        new = torch.empty(self.P, dtype=torch.float32, device=dev)
+        use_alpha = self.alpha is not None
+        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), old.data_ptr(),
+                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
+                                         float(self.n_step_size), self.min_log_std, new.data_ptr(),
+                                         res[:3].data_ptr(), c.stream), "amx_npg_apply_step")
+        self._pass(NPG_EVAL, obs, act, adv, new, out=res[3:5])
+        if bc is not None:
+            self.log_likelihood(bc[0], bc[1], new, out=res[9:10])
+        out = {}
+        if dist_info:
+            _, ll_o, mean_o = self.log_likelihood(obs, act, old, rows=True)
+            _, ll_n, mean_n = self.log_likelihood(obs, act, new, rows=True)
+            out = {"old_dist_info": [ll_o, mean_o, old[-self.A:].clone()],
+                   "new_dist_info": [ll_n, mean_n, new[-self.A:].clone()], "lr": torch.exp(ll_n - ll_o)}
+        self.theta = new
+        if self.policy is not None:
+            self.policy.sync_from(*self._layers_view())
+        alpha_h, delta_h, _, surr_h, kl_h, sb_h, _, count_h, lle_o, lle_n = res.tolist()  # the one host sync
+        self.hvp_products = int(count_h) if idx is not None else 0
+        if states is not None:  # the reference's loop stops drawing at its break (cg_solve.py:19-20)
+            np.random.set_state(states[self.hvp_products])
+        reg, ne = (bc[2], bc[0].shape[0]) if bc is not None else (0.0, 1)
+        out.update({"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h,
+                    "surr_before": sb_h / n + reg * lle_o / ne, "surr_after": surr_h / n + reg * lle_n / ne,
+                    "kl_dist": kl_h / n, "advantages": adv, "hvp_products": self.hvp_products})
+        return out
+
     def train_from_paths(self, paths, infos: dict | None = None):
         """Reference surface: mjrl path dicts (observations, actions, advantages, rewards) ->
         base_stats [mean, std, min, max] of path returns; infos updated as the reference's."""
@@ -322,3 +526,127 @@ class DeviceNPG:
         obs = engine.obs[:T].reshape(T * B, self.S)
         act = engine.acts[:T].reshape(T * B, self.A)
         return self.train_from_arrays(obs, act, advantages.reshape(T * B))
+
+
+class NPG:
+    """mjrl's NPG (npg_cg.py:25-199) with the update on the device: the reference's constructor,
+    attributes, `train_from_paths(paths, infos)` and logger.  `policy`: an mjrl MLP or any object
+    with its attribute layout (see ppo.PPO).  `ctx`: the AmxContext to run on (one is made for the
+    policy's sizes when None).  train_step and the rollout statistics come from the reference's
+    BatchREINFORCE: `class NPG(amx.NPG, BatchREINFORCE): pass`."""
+
+    def __init__(self, env, policy, baseline, normalized_step_size=0.01, const_learn_rate=None,
+                 FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
+                 kl_dist=None, input_normalization=None,
+                 bc_args={'flag': False, 'expert_paths': None, 'reg_coeff': None}, ctx=None, **kwargs):
+        from .bc import HIDDEN, DataLog
+        tr = getattr(policy.model, "transformations", None)
+        if tr and any(x is not None for x in tr.values()):
+            raise NotImplementedError("the policy's model has input / output transformations: the device policy "
+                                      "assumes identity transformations")
+        hidden = tuple(l.weight.shape[0] for l in list(policy.model.fc_layers)[:-1])
+        if hidden != HIDDEN:
+            raise NotImplementedError(f"the device update supports hidden sizes {HIDDEN}, not {hidden}")
+        # the reference ignores values outside (0, 1] (npg_cg.py:61-63)
+        if input_normalization is not None and 0 < input_normalization <= 1:
+            raise NotImplementedError("running input normalization is not implemented")
+        self.env = env
+        self.policy = policy
+        self.baseline = baseline
+        self.alpha = const_learn_rate
+        self.n_step_size = normalized_step_size if kl_dist is None else 2.0 * kl_dist
+        self.seed = seed
+        self.save_logs = save_logs
+        self.FIM_invert_args = FIM_invert_args
+        self.hvp_subsample = hvp_sample_frac
+        self.running_score = None
+        self.logger = DataLog()
+        self.input_normalization = None
+        self.bc_args = bc_args
+        self.ctx = ctx
+        self.device_npg = None
+        self._expert = None  # (host obs, host act, device obs, device act)
+
+    def _device_npg(self) -> DeviceNPG:
+        """The engine object, built on first use; this object's current settings."""
+        pol = self.policy
+        layers = [(l.weight, l.bias) for l in pol.model.fc_layers]
+        S, A = layers[0][0].shape[1], layers[-1][0].shape[0]
+        if self.ctx is None:
+            self.ctx = AmxContext(S, A)
+        if (self.ctx.S, self.ctx.A) != (S, A):
+            raise ValueError("the policy's sizes do not match the context's S, A")
+        if self.device_npg is None:
+            self.device_npg = DeviceNPG(self.ctx, layers, pol.log_std, min_log_std=float(pol.min_log_std))
+        d = self.device_npg
+        d.alpha, d.n_step_size, d.hvp_subsample = self.alpha, self.n_step_size, self.hvp_subsample
+        d.cg_iters, d.damping = int(self.FIM_invert_args["iters"]), float(self.FIM_invert_args["damping"])
+        d.dist_info = d.eval_before = True
+        return d
+
+    def _bc(self, d: DeviceNPG):
+        """The expert rows on the device: uploaded once, again only when the arrays change."""
+        b = self.bc_args
+        if not b or not b.get("flag"):
+            return None
+        eo, ea = np.asarray(b["expert_paths"]["observations"]), np.asarray(b["expert_paths"]["actions"])
+        e = self._expert
+        if e is None or not (np.array_equal(e[0], eo) and np.array_equal(e[1], ea)):
+            do, da, _ = d._inputs(eo, ea)
+            e = self._expert = (eo.copy(), ea.copy(), do, da)
+        return e[2], e[3], float(b["reg_coeff"])
+
+    def train_from_paths(self, paths, infos):
+        pol = self.policy
+        # BatchREINFORCE.process_paths (batch_reinforce.py:271-297)
+        observations = np.concatenate([path["observations"] for path in paths])
+        actions = np.concatenate([path["actions"] for path in paths])
+        advantages = np.concatenate([path["advantages"] for path in paths])
+        advantages = (advantages - np.mean(advantages)) / (np.std(advantages) + 1e-6)
+        path_returns = [sum(p["rewards"]) for p in paths]
+        mean_return = np.mean(path_returns)
+        base_stats = [mean_return, np.std(path_returns), np.amin(path_returns), np.amax(path_returns)]
+        self.running_score = mean_return if self.running_score is None else \
+            0.9 * self.running_score + 0.1 * mean_return
+        infos['advantages'] = advantages
+        if self.save_logs and hasattr(self, "log_rollout_statistics"):
+            self.log_rollout_statistics(paths)
+
+        # the device update differentiates at new == old, as the reference's write-back leaves them
+        cur = pol.get_param_values()
+        old = np.concatenate([np.asarray(p.data.reshape(-1)) for p in pol.old_params])
+        if not np.array_equal(cur, old):
+            raise ValueError("policy.old_params differ from policy.trainable_params: the NPG update starts from "
+                             "new == old (set_param_values(..., set_new=True, set_old=True))")
+        ts = timer.time()
+        d = self._device_npg()
+        d.theta = torch.from_numpy(np.asarray(cur, dtype=np.float32)).to(d.ctx.device)  # as the policy holds them
+        out = d.train_from_arrays(observations, actions, advantages, whiten=False, bc=self._bc(d))
+        new_params = d.theta.cpu().numpy()
+        pol.set_param_values(new_params, set_new=True, set_old=True)
+        t_upd = timer.time() - ts
+
+        f32 = np.float32
+        surr_before, surr_after, kl_dist = f32(out["surr_before"]), f32(out["surr_after"]), f32(out["kl_dist"])
+        infos['old_dist_info'] = [t.cpu() for t in out["old_dist_info"]]
+        infos['new_dist_info'] = [t.cpu() for t in out["new_dist_info"]]
+        infos['lr'] = out["lr"].cpu()
+        infos['surr_before'] = surr_before
+        if self.alpha is None:  # (npg_cg.py:157-161)
+            infos['vpg_grad'] = out["vpg_grad"].cpu().numpy().astype(f32)
+            infos['npg_grad'] = out["npg_grad"].cpu().numpy().astype(f32)
+        infos['surr_after'] = surr_after
+        if self.save_logs:
+            self.logger.log_kv('alpha', out["alpha"])
+            self.logger.log_kv('delta', out["delta"])
+            # one device update: the gradient and the solve are not timed apart
+            self.logger.log_kv('time_vpg', 0.0)
+            self.logger.log_kv('time_npg', t_upd)
+            self.logger.log_kv('kl_dist', kl_dist)
+            self.logger.log_kv('surr_improvement', surr_after - surr_before)
+            self.logger.log_kv('running_score', self.running_score)
+            infos['surr_improvement'] = surr_after - surr_before
+            infos['running_score'] = self.running_score
+            infos['kl_dist'] = kl_dist
+            infos['alpha'] = out["alpha"]
+        return base_stats

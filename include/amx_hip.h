@@ -382,6 +382,31 @@ int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dtype, long lo
                     int rows_per_block, double* partials, float* hcache, double tol, double* x, const double* r_in,
                     double* r_out, const double* p_in, double* p_out, float* p32_out, const double* state_in,
                     double* state_out, const double* work, void* stream);
+/* The Fisher-vector pass over an index vector: NPG.HVP with hvp_sample_frac < 1
+ * (mjrl/mjrl/algos/npg_cg.py:90-94).  row_idx: device int32 [M], 0 <= row_idx[k] < N (the caller
+ * guarantees the range; duplicates are legal, the reference samples with replacement).  The pass
+ * runs over the M rows obs[row_idx[k]], divides by M and, with hcache ([N][64], written by the
+ * VPG pass over all N rows), reads hcache[row_idx[k]]: the partials ([ceil(M / rows_per_block)][P])
+ * are those of amx_npg_pass_ex (mode 1) on the materialised rows, bit for bit.  fp32 observations
+ * only (obs_dtype AMX_IN_F32).  prod_count (optional, device double): += 1 when the product is
+ * taken (not gated, not stopped) -- the solve's count of index vectors consumed.
+ * amx_npg_pass_cg_idx is amx_npg_pass_cg over the index vector. */
+int amx_npg_pass_idx(amx_ctx* ctx, int N, int M, const int32_t* row_idx, const void* obs, int obs_dtype,
+                     long long ldo, const float* theta, const float* vec, int rows_per_block, double* partials,
+                     const double* gate, float* hcache, double* prod_count, void* stream);
+int amx_npg_pass_cg_idx(amx_ctx* ctx, int N, int M, const int32_t* row_idx, const void* obs, int obs_dtype,
+                        long long ldo, const float* theta, int rows_per_block, double* partials, float* hcache,
+                        double tol, double* x, const double* r_in, double* r_out, const double* p_in,
+                        double* p_out, float* p32_out, const double* state_in, double* state_out,
+                        const double* work, double* prod_count, void* stream);
+/* The log-likelihood pass of NPG.CPI_surrogate's BC term and dist-info entries
+ * (gaussian_mlp.py:106-122 in fp32): amx_ppo_old_ll's rows and arithmetic (the same LL bits, so
+ * equal parameters give LL_new - LL_old == 0 and a likelihood ratio of exactly 1).
+ * partials[b] (device fp64 [amx_npg_ll_blocks(ctx, N)]) = the sum of workgroup b's rows' LL;
+ * ll (optional, fp32 [N]) and mean (optional, fp32 [N][A]) take every row's LL and policy mean. */
+int amx_npg_ll_blocks(amx_ctx* ctx, int N);
+int amx_npg_ll(amx_ctx* ctx, int N, const float* obs, long long ldo, const float* act, long long lda,
+               const float* theta, double* partials, float* ll, float* mean, void* stream);
 int amx_npg_cg_init(amx_ctx* ctx, int P, const double* b, double* x, double* r, double* p, float* p32,
                     double* state, void* stream);
 /* amx_npg_cg_init + amx_npg_curvature (theta's log_std block -> curv [A]) in one launch. */
