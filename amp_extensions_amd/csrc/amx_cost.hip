@@ -467,6 +467,7 @@ extern "C" int amx_expert_cost(amx_ctx* ctx, const float* phi_e_rows, int ldphi,
                                void* stream) {
   AMX_CHECK_ARG(ctx && phi_e_rows && w && out, "amx_expert_cost: null pointer");
   AMX_CHECK_ARG(F > 0 && F % 128 == 0 && ldphi >= F && ldphi % 4 == 0, "amx_expert_cost: F=%d ldphi=%d", F, ldphi);
+  AMX_CHECK_ARG(amx::aligned16(phi_e_rows) && amx::aligned16(w), "amx_expert_cost: rows/w must be 16-byte aligned");
   AMX_CHECK_ARG(n > 0, "amx_expert_cost: n=%d", n);
   // partials live in out[1 .. nb]; out must hold 1 + 1024 doubles
   const int nb = expert_blocks(n);

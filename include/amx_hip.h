@@ -607,7 +607,8 @@ int amx_mmd_reward_raw(amx_ctx* ctx, const float* phi, int ldphi, const float* w
 /* get_expert_cost (milo/milo/linear_cost.py:105-109): partial fp64 sums over row
  * blocks of clamp(phi_E[r].w, c_min, c_max); out[0] = sum (fp64; out holds 1 + 1024
  * doubles).  mean_out (nullable) receives the finished cost in fp32:
- * (float)(1 - lambda_b) * (float)(sum / n).  Uses the resident expert features. */
+ * (float)(1 - lambda_b) * (float)(sum / n).  Uses the resident expert features.
+ * phi_e_rows and w are 16-byte aligned, ldphi a multiple of 4 (float4 loads). */
 int amx_expert_cost(amx_ctx* ctx, const float* phi_e_rows, int ldphi, const float* w, int F, int n,
                     float c_min, float c_max, double* out, float* mean_out, double lambda_b,
                     void* stream);
