@@ -7,7 +7,9 @@ gfx950 behind a C ABI (include/amx_hip.h, libamx_hip.so) and the reference's Pyt
 surfaces (SimEnv, sample_points, RBFLinearCost, MLPCost, GAILCost, DynamicsEnsemble), plus the
 sampler's consumers: returns, MLP value baseline (prediction and the mini-batch Adam fit) and
 GAE (mjrl process_samples, MLPBaseline), the NPG and PPO policy updates (mjrl npg_cg, ppo_clip)
-and the behaviour-cloning warm start (mjrl BC).
+and the behaviour-cloning warm start (mjrl BC), and the evaluation's DTW score of a rollout against
+the reference motion (DeepMimicCore's time warper; TimeWarper, and evaluate.evaluate: the
+submodule keeps the function's name, so it is imported from there).
 
 The native library is loaded on first use; there is no CPU fallback.
 """
@@ -18,7 +20,7 @@ __all__ = [
     "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
     "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
-    "PPO", "DevicePPO", "NPG",
+    "PPO", "DevicePPO", "NPG", "TimeWarper",
 ]
 
 
@@ -53,6 +55,9 @@ def __getattr__(name):
     if name in ("PPO", "DevicePPO"):
         from . import ppo
         return getattr(ppo, name)
+    if name == "TimeWarper":
+        from .dtw import TimeWarper
+        return TimeWarper
     if name == "sample_points":
         from .sampler import sample_points
         return sample_points

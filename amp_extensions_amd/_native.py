@@ -82,6 +82,11 @@ SIGNATURES = {
     "amx_state_amp_obs": (c_int, [vp, vp, vp, c_ll, c_int, c_int, vp, c_ll, vp]),
     "amx_motion_amp_obs": (c_int, [vp, vp, c_dbl, c_int, c_int, vp, c_ll, vp]),
     "amx_state_amp_rows": (c_int, [vp, vp, vp, c_ll, c_int, c_int, vp, c_ll, vp]),
+    "amx_tw_dim": (c_int, [vp]),
+    "amx_state_tw_rows": (c_int, [vp, vp, c_ll, c_int, c_int, vp, c_ll, vp]),
+    "amx_motion_tw_rows": (c_int, [vp, vp, vp, c_int, c_int, c_dbl, vp, c_ll, vp]),
+    "amx_dtw_work": (c_ll, [c_int, c_int]),
+    "amx_dtw_align": (c_int, [vp, vp, vp, c_ll, c_int, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, vp, vp, vp]),
     "amx_npg_param_count": (c_ll, [c_int, c_int]),
     "amx_npg_pass": (c_int, [vp, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, vp, c_int, vp, vp]),
     "amx_npg_reduce": (c_int, [vp, vp, c_int, c_int, vp, vp]),
@@ -182,6 +187,7 @@ AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
 AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1
 AMX_DFIT_SGD, AMX_DFIT_ADAM = 0, 1
 AMX_BC_MSE, AMX_BC_MLE = 0, 1
+AMX_DTW_COST_SQUARED, AMX_DTW_COST_POINTS = 0, 1
 AMX_PPO_OLD_SNAPSHOT, AMX_PPO_OLD_TRACKS_MEAN = 0, 1
 
 

@@ -785,6 +785,81 @@ __global__ __launch_bounds__(64) void k_motion_amp_obs(const double* __restrict_
   amp_obs(m, kp, kc, local_root != 0, out + (long long)b * ldo);
 }
 
+// ---- time-warp rows (cSceneImitateAMP::BuildTimeWarpData, scenes/SceneImitateAMP.cpp:537-555) --
+// row = [(0, root_y, 0), joint_j world position - root joint world position for j >= 1]: what
+// the DTW evaluation compares between the simulated and the kinematic character (amx_dtw.hip).
+//
+// From a recorded state (RecordWorldRootRot): the state holds the body positions in the heading
+// frame relative to the root joint, pp_j = Rh (o_j + R_j attach_body_j - o_0), and the body
+// rotations R^h_j = Rh R_j as tangent-normal pairs, so o_j - o_0 = Rh^T (pp_j - R^h_j attach_body_j).
+// 16 threads per row (thread j: joint j), four rows per workgroup, as k_state_amp_obs.
+__global__ __launch_bounds__(64) void k_state_tw_rows(const double* __restrict__ blob, const double* __restrict__ st,
+                                                      long long lds, int B, double* __restrict__ out, long long ldo) {
+  __shared__ double hdr[HDR], jtab[8 * MAXJ], btab[8 * MAXJ];
+  const int j = threadIdx.x & 15;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 4);
+  const MView m = stage_tables(blob, hdr, jtab, btab);
+  if (b >= B || j >= m.J) return;
+  const double* s = st + (long long)b * lds;
+  double* o = out + (long long)b * ldo;
+  if (j == 0) {
+    o[0] = 0.0; o[1] = s[0]; o[2] = 0.0;
+    return;
+  }
+  double Rw0[9], Rh[9], Rj[9];
+  tn_mat(s + 4, Rw0);
+  heading_of(Rw0, Rh);
+  tn_mat(s + 9 * j + 4, Rj);
+  const double* bd = m.bodies + 8 * j;
+  const V3 d = mtv(Rh, sub({s[9 * j + 1], s[9 * j + 2], s[9 * j + 3]}, mv(Rj, {bd[1], bd[2], bd[3]})));
+  o[3 * j] = d.x; o[3 * j + 1] = d.y; o[3 * j + 2] = d.z;
+}
+
+// From the clip: row i of trajectory t is the kinematic character at t0[t] + i / update_rate,
+// the pose of the reset path (clip_frame + the loop's cycle offset, as motion_state), its joint
+// origins as kin_from_pose walks them; root height = the clip's + lift[t] (SyncKinCharRoot copies
+// the ground-resolved root position to the kinematic character, scenes/SceneImitate.cpp:550-582)
+// until a looping clip starts its next cycle: SyncKinCharNewCycle (:400-412, 594-607) then puts
+// the root back at ground height + the clip's height over its origin, which on the plane drops
+// the lift for the rest of the episode.  One thread per row.
+__global__ __launch_bounds__(64) void k_motion_tw_rows(const double* __restrict__ blob, const double* __restrict__ t0,
+                                                       const double* __restrict__ lift, int T, int n, double rate,
+                                                       double* __restrict__ out, long long ldo) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= (long long)T * n) return;
+  const int t = (int)(r / n), i = (int)(r % n);
+  const MView m(blob);
+  const double time = t0[t] + i / rate;
+  double pose[MAXD], vel[MAXD];
+  clip_frame(m, time, pose, vel);
+  double root_y = pose[1];
+  if (m.h[3] != 0.0) root_y += floor(time / m.h[4]) * m.h[9];
+  if (lift && (m.h[3] == 0.0 || floor(time / m.h[4]) == floor(t0[t] / m.h[4]))) root_y += lift[t];
+  double R[MAXJ][9];
+  V3 o[MAXJ];
+  qmat(ldq(pose + 3), R[0]);
+  o[0] = {pose[0], pose[1], pose[2]};
+  double* q = out + r * ldo;
+  q[0] = 0.0; q[1] = root_y; q[2] = 0.0;
+  for (int j = 1; j < m.J; ++j) {
+    const double* jt = m.joints + 8 * j;
+    const int type = (int)jt[0], par = (int)jt[1], off = (int)jt[2];
+    o[j] = add(o[par], mv(R[par], {jt[4], jt[5], jt[6]}));
+    double L[9];
+    if (type == JT_SPHERICAL) {
+      qmat(ldq(pose + off), L);
+      mm(R[par], L, R[j]);
+    } else if (type == JT_REVOLUTE) {
+      axis_mat({0.0, 0.0, 1.0}, pose[off], L);
+      mm(R[par], L, R[j]);
+    } else {
+      for (int k = 0; k < 9; ++k) R[j][k] = R[par][k];
+    }
+    const V3 d = sub(o[j], o[0]);
+    q[3 * j] = d.x; q[3 * j + 1] = d.y; q[3 * j + 2] = d.z;
+  }
+}
+
 // one 64-thread workgroup per lane (motion_state)
 __global__ __launch_bounds__(64) void k_motion_states(const double* __restrict__ blob, const double* __restrict__ times,
                                                       int B, int flags, double* __restrict__ ob, long long ldo,
@@ -1000,6 +1075,36 @@ extern "C" int amx_motion_amp_obs(amx_ctx* c, const double* times, double dt, in
   if (B == 0) return AMX_OK;
   hipLaunchKernelGGL(k_motion_amp_obs, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, c->d_motion, times,
                      dt, B, local_root, out, ldo);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+// ---- time-warp rows ---------------------------------------------------------------------------
+extern "C" int amx_tw_dim(const amx_ctx* c) { return (c && c->d_motion) ? 3 * c->motion_J : -1; }
+
+extern "C" int amx_state_tw_rows(amx_ctx* c, const double* s, long long lds, int B, int flags, double* out,
+                                 long long ldo, void* stream) {
+  AMX_CHECK_ARG(c && c->d_motion, "amx_state_tw_rows: no character set (amx_set_motion)");
+  AMX_CHECK_ARG(flags == 2, "amx_state_tw_rows: record flags %d; the rows need RecordWorldRootRot only (2)", flags);
+  AMX_CHECK_ARG(s && out && B >= 0 && lds >= c->S && ldo >= 3 * c->motion_J,
+                "amx_state_tw_rows: bad arguments (lds=%lld ldo=%lld)", lds, ldo);
+  if (B == 0) return AMX_OK;
+  hipLaunchKernelGGL(k_state_tw_rows, dim3((B + 3) / 4), dim3(64), 0, (hipStream_t)stream, c->d_motion, s, lds, B, out,
+                     ldo);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+extern "C" int amx_motion_tw_rows(amx_ctx* c, const double* t0, const double* lift, int T, int n, double update_rate,
+                                  double* out, long long ldo, void* stream) {
+  AMX_CHECK_ARG(c && c->d_motion, "amx_motion_tw_rows: no motion set (amx_set_motion)");
+  AMX_CHECK_ARG(t0 && out && T >= 0 && n >= 0 && ldo >= 3 * c->motion_J && update_rate > 0.0,
+                "amx_motion_tw_rows: bad arguments (T=%d n=%d ldo=%lld update_rate=%g)", T, n, ldo, update_rate);
+  const long long rows = (long long)T * n;
+  AMX_CHECK_ARG(rows <= 0x7FFFFFFFLL / 64, "amx_motion_tw_rows: %lld rows", rows);
+  if (rows == 0) return AMX_OK;
+  hipLaunchKernelGGL(k_motion_tw_rows, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                     c->d_motion, t0, lift, T, n, update_rate, out, ldo);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
 }

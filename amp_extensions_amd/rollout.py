@@ -187,16 +187,18 @@ class RolloutEngine:
                                                    None if t_out is None else t_out.data_ptr(),
                                                    self.B, c.stream), "amx_reset_lanes_motion_noise")
 
-    def reset_lanes(self, mask: torch.Tensor | None, rows: torch.Tensor | None = None) -> None:
+    def reset_lanes(self, mask: torch.Tensor | None, rows: torch.Tensor | None = None,
+                    t_out: torch.Tensor | None = None) -> None:
         """SimEnv.reset on the lanes with mask != 0 (all lanes when mask is None); the lane
         states are taken from (and written back to) slot 0 of a fresh rollout.  With a
         ReferenceMotion reset source, `rows` are motion times [B] float64 (None: drawn
-        uniform(0, duration) per lane from Philox)."""
+        uniform(0, duration) per lane from Philox; t_out [B] float64 receives every reset lane's
+        time, -1 for the others)."""
         c = self.ctx
         self.begin_rollout()
         dst = self.obs[0]
         if self.motion is not None:
-            self._reset_motion(mask, rows, dst, dst, None)
+            self._reset_motion(mask, rows, dst, dst, t_out)
             self.t = 0
             return
         N.check(c.lib.amx_reset_lanes(c.h, None if mask is None else mask.data_ptr(), self.table.data_ptr(),

@@ -53,7 +53,7 @@ def _gym_np_random(seed: int) -> np.random.Generator:
 
 
 class _Traj:
-    __slots__ = ("worker", "j", "seed", "lane", "length", "ended", "segs")
+    __slots__ = ("worker", "j", "seed", "lane", "length", "ended", "segs", "reset_time")
 
     def __init__(self, worker: int, j: int, seed: int):
         self.worker, self.j, self.seed = worker, j, seed
@@ -61,6 +61,7 @@ class _Traj:
         self.length = 0       # transitions so far (the final length once ended)
         self.ended = False
         self.segs = []  # (store row, count) pieces in step order
+        self.reset_time = None  # the clip time (table row) its reset drew, where the host knows it
 
 
 class _Store:
@@ -501,6 +502,20 @@ def _build_paths(trajs, store, eng: RolloutEngine, dev):
     return paths, off
 
 
+def _deliver_dtw(dtw, trajs, paths) -> None:
+    """The evaluation's deliveries (gym_deepmimic.py:160-162): path['reset_time'] and the last
+    env_info's 'dtw_cost', scored in one launch from the device rows the paths were copied from."""
+    obs, nxt = _last_rows["observations"][1], _last_rows["next_observations"][1]
+    states, off = [], 0
+    for tr in trajs:
+        states.append(torch.cat([obs[off:off + tr.length], nxt[off + tr.length - 1:off + tr.length]], dim=0))
+        off += tr.length
+    cost = dtw.score(states, [tr.reset_time for tr in trajs])["dtw_cost"].cpu().numpy()
+    for tr, p, c in zip(trajs, paths, cost):
+        p["reset_time"] = tr.reset_time
+        p["env_infos"][-1]["dtw_cost"] = float(c)
+
+
 def _chunk_graph(eng: RolloutEngine, K: int, noise_dev, eval_mode: bool) -> _ChunkGraph:
     """The chunk's captured graph, cached on the engine across sample_points calls: it bakes in
     the engine's and the policy's device buffers (persistent; DevicePolicy.sync_from rewrites
@@ -567,10 +582,12 @@ class _Stage:
 
 
 def _reset_lanes(eng: RolloutEngine, st: _Stage, devs, active: np.ndarray, new: list, rng: str,
-                 time_max: float) -> None:
+                 time_max: float, t_out: torch.Tensor | None = None) -> None:
     """A chunk's resets: the new trajectories' lanes (reset counter j - 1 -> member j mod M; with
     rng='reference' at the reset time drawn from the trajectory's seed) and the idle lanes, staged
-    in `st` and uploaded into devs = (mask, counts, rows) without a host wait."""
+    in `st` and uploaded into devs = (mask, counts, rows) without a host wait.  t_out ([L] float64,
+    the DTW score's request with rng='device'): the times the device drew are read back into the
+    new trajectories (one host wait)."""
     mask_dev, counts_dev, rows_dev = devs
     mask_np, counts_np, rows_np = st.mask.numpy(), st.counts.numpy(), st.rows.numpy()
     eng.begin_rollout()
@@ -583,17 +600,22 @@ def _reset_lanes(eng: RolloutEngine, st: _Stage, devs, active: np.ndarray, new: 
         if rng == "reference":
             t = _gym_np_random(tr.seed).uniform(low=0, high=time_max)  # seed_env + reset (sim_env.py:132,276)
             rows_np[tr.lane] = t if eng.motion is not None else int(np.floor(t))
+            tr.reset_time = float(t)
     mask_dev.copy_(st.mask, non_blocking=True)
     counts_dev.copy_(st.counts, non_blocking=True)
     # reset lanes restart their counter at j - 1 (idle lanes at 0); the reset kernel adds one
     torch.where(mask_dev.bool(), counts_dev, eng.reset_count, out=eng.reset_count)
     if rng == "reference":
         rows_dev.copy_(st.rows, non_blocking=True)
-    eng.reset_lanes(mask_dev, rows_dev if rng == "reference" else None)
+    eng.reset_lanes(mask_dev, rows_dev if rng == "reference" else None, t_out=t_out)
+    if t_out is not None and rng != "reference" and new:
+        drawn = t_out.cpu().numpy()
+        for tr in new:
+            tr.reset_time = float(drawn[tr.lane])
 
 
 def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, rng: str, eval_mode: bool,
-             time_max: float, speculate: bool = True, graph: bool = True, pipeline: bool = True):
+             time_max: float, speculate: bool = True, graph: bool = True, pipeline: bool = True, dtw=None):
     """Run the W workers' trajectory sequences on the engine's lanes (see the module notes and
     _Admission): admit, launch a chunk (resets, noise, the K steps), read a chunk back (its done
     flags; its in-flight rows compacted into the store; its trajectories advanced).
@@ -621,6 +643,8 @@ def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, 
     stage = [_Stage(L, K, rows_dtype, dev, pipeline) for _ in range(2 if pipeline else 1)]
     reset_devs = (torch.empty(L, dtype=torch.uint8, device=dev), torch.empty(L, dtype=torch.int32, device=dev),
                   torch.empty(L, dtype=rows_dtype, device=dev))
+    # (the DTW score needs every trajectory's reset time; the reference draw is the host's already)
+    t_out = torch.empty(L, dtype=torch.float64, device=dev) if dtw is not None and rng != "reference" else None
     pre_drawn = False  # the lanes of the previous chunk already hold their next K draws
     chunk_graph = None
     chunks, budget = 0, 4 * (W * quota + W) * (R + K) // K + 64
@@ -671,7 +695,7 @@ def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, 
         st = stage[si]
         active = np.array([b for b, _ in launched], np.int64)
         new_lanes = np.array([tr.lane for tr in new], np.int64)
-        _reset_lanes(eng, st, reset_devs, active, new, rng, time_max)
+        _reset_lanes(eng, st, reset_devs, active, new, rng, time_max, t_out)
         # ---- K synchronous steps ----
         if hn is not None:
             hn.join()
@@ -713,13 +737,16 @@ def _collect(eng: RolloutEngine, W: int, quota: int, mode: str, base_seed: int, 
     trajs = adm.trajectories()
     if not trajs:
         return [], 0
-    return _build_paths(trajs, store, eng, dev)
+    paths, n = _build_paths(trajs, store, eng, dev)
+    if dtw is not None:
+        _deliver_dtw(dtw, trajs, paths)
+    return paths, n
 
 
 def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_workers: int = 4, mode: str = "samples",
                   eval_mode: bool = False, verbose: bool = False, deepmimic: bool = False, rng: str = "reference",
                   chunk: int = 16, speculate: bool = True, graph: bool = True, pipeline: bool = True,
-                  member_blocked: bool = True):
+                  member_blocked: bool = True, dtw=None):
     """milo.sampler.sample_points on the GPU.  `env` is a BatchedSimEnv (or a RolloutEngine):
     its ensemble, reset source, reset-time window (reset_args custom_time / time_max) and
     termination are used, and its lane count caps the concurrency; `policy` a DevicePolicy or
@@ -733,7 +760,10 @@ def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_work
     _collect); `member_blocked` (f16x3 ensembles with M >= 2): every lane steps through
     its trajectory's member only, as SimEnv.step does (the engine's lanes in M blocks of a
     multiple of 128; a quarter of the ensemble rows per step at M = 4), instead of all M members
-    on every lane (same paths up to the GEMM's fp32 rounding)."""
+    on every lane (same paths up to the GEMM's fp32 rounding).  `dtw` (a dtw.TimeWarper on the
+    env's ReferenceMotion): every path also carries path['reset_time'] and
+    env_infos[-1]['dtw_cost'], the evaluation's score as gym_deepmimic.py:160-162 delivers it;
+    without it the dicts hold neither key."""
     assert mode == "samples" or mode == "trajectories"
     if rng not in ("reference", "device"):
         raise ValueError("rng must be 'reference' or 'device'")
@@ -757,13 +787,15 @@ def sample_points(env, policy, num_to_collect: int, base_seed: int = 0, num_work
         lanes = M * Bq
     K = max(1, min(int(chunk), R))
     time_max = _reset_time_max(env)
+    if dtw is not None and src.motion is None:
+        raise ValueError("sample_points: dtw needs a ReferenceMotion reset source (the score aligns with the clip)")
     policy = device_policy(env, policy)
     eng = _sampler_engine(env, lanes, K, policy, time_max, Bq)
     if rng == "device":
         policy.seed = (12345 + int(base_seed)) & 0xFFFFFFFFFFFFFFFF
     t0 = time.time()
     paths, n = (_collect(eng, W, quota, mode, int(base_seed), rng, eval_mode, time_max, speculate=speculate,
-                         graph=graph, pipeline=pipeline)
+                         graph=graph, pipeline=pipeline, dtw=dtw)
                 if quota > 0 else ([], 0))
     if verbose:
         print(f"Collected {n} and {len(paths)} trajectories in {time.time() - t0} seconds")

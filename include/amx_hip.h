@@ -291,6 +291,47 @@ int amx_motion_amp_obs(amx_ctx* ctx, const double* times, double dt, int B, int 
 int amx_state_amp_rows(amx_ctx* ctx, const double* s_prev, const double* s_cur, long long lds, int B,
                        int local_root, float* out, long long ldo, void* stream);
 
+/* ---- DTW evaluation (the 'dtw_cost' of an imitate_amp run; milo/milo/utils.py:115-217) ----
+ * Time-warp rows (cSceneImitateAMP::BuildTimeWarpData, scenes/SceneImitateAMP.cpp:537-555):
+ * amx_tw_dim = 3 J doubles per row, [(0, root_y, 0), joint_j - root joint (world) for j >= 1].
+ *   amx_state_tw_rows:  from recorded SimEnv states s [B][lds]; `flags` are the record flags
+ *                       of the states and must be 2 (RecordWorldRootRot only);
+ *   amx_motion_tw_rows: of the kinematic character: row t * n + i is the clip pose at
+ *                       t0[t] + i / update_rate with lift[t] added to the root height (the
+ *                       trajectory's ground-resolve lift; null: none) while a looping clip is
+ *                       in the cycle it was reset in (SyncKinCharNewCycle drops it at the next,
+ *                       scenes/SceneImitate.cpp:594-607).  out [T * n][ldo]. */
+int amx_tw_dim(const amx_ctx* ctx);
+int amx_state_tw_rows(amx_ctx* ctx, const double* s, long long lds, int B, int flags, double* out,
+                      long long ldo, void* stream);
+int amx_motion_tw_rows(amx_ctx* ctx, const double* t0, const double* lift, int T, int n, double update_rate,
+                       double* out, long long ldo, void* stream);
+/* cDynamicTimeWarper (DeepMimicCore/util/DynamicTimeWarper.cpp: CalcAlignment, CalcIndexBuffer,
+ * AddRemainderCost) for T trajectories in one launch, one workgroup each.  `cost_kind` is the cell
+ * cost: AMX_DTW_COST_POINTS = cSceneImitateAMP::TimeWarpCost (SceneImitateAMP.cpp:5-25; the
+ * mean Euclidean distance of the rows' dim / 3 points, what the scene's warper is built with and
+ * the reported 'dtw_cost' uses; dim % 3 == 0), AMX_DTW_COST_SQUARED = the warper's DefaultCost
+ * (DynamicTimeWarper.cpp:3-8; the squared distance of the rows).  data0 / data1
+ * [T][n_max][ld] fp64 rows of width dim (simulated / kinematic); trajectory t uses its first
+ * len[t] rows of both (2 <= len <= n_max <= 513: a thread per row).  len_host is a HOST array the call validates,
+ * len the caller's device copy of it the kernel reads (clamped into [2, n_max] there; that
+ * the two copies agree is the caller's responsibility: nothing on the launch path can compare them).
+ * work: amx_dtw_work(T, n_max) doubles (every trajectory's n_max x n_max cost buffer).
+ * Outputs: cost [T] = C(n-1, n-1); dtw_cost [T] (nullable) = cost + remainder, remainder =
+ * buffer_size - len (SceneImitateAMP.cpp:261-269); index [T][n_max] int32 and backtrack
+ * [T][n_max] (after the remainder; backtrack_raw, nullable: before it), entries [0, len) only.
+ * Bad arguments (null pointer, ld < dim, a len outside [2, n_max], buffer_size < len, n_max
+ * above 513, an LDS need of (3 n_max + 96 dim) doubles above 64 KiB) return AMX_E_ARG before
+ * any launch. */
+#define AMX_E_ARG AMX_E_INVAL
+enum { AMX_DTW_COST_SQUARED = 0, AMX_DTW_COST_POINTS = 1 };
+long long amx_dtw_work(int T, int n_max);
+int amx_dtw_align(amx_ctx* ctx, const double* data0, const double* data1, long long ld, int dim, int cost_kind,
+                  int n_max,
+                  const int32_t* len_host, const int32_t* len, int T, int buffer_size, double* work,
+                  double* cost, double* dtw_cost, int32_t* index, double* backtrack_raw, double* backtrack,
+                  void* stream);
+
 /* ---- NPG policy update (the rollout's learner; mjrl/mjrl/algos/npg_cg.py:113-199) ----
  * Policy: mjrl MLP(S -> 32 -> 32 -> A, tanh) + log_std (mjrl/mjrl/policies/gaussian_mlp.py),
  * parameters packed in the reference's flat order (W1, b1, W2, b2, W3, b3, log_std; fp32,
