@@ -306,7 +306,7 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
   // JJM: layer-1 K steps compiled (>= ceil(S / 16); steps past S multiply zero weights)
   // HC (FVP): the theta forward (H1, H2) is read from a.hcache, written by the VPG pass of the
   // same update (same kernels, same bits), instead of recomputed: layer 1 computes only the
-  // tangent's tiles, its two MFMA chains (x.x/x.z and x.y/x.w) on two waves each, and layer 2's
+  // tangent's tiles, its four MFMA chains (x.x, x.z | x.y, x.w) on two waves each, and layer 2's
   // two products of the tangent (H1 V2^T and D1' W2^T) on two waves -- every sum in the order
   // of the uncached pass, so the products are bit-identical to it
   constexpr int mode = MODE;
@@ -535,13 +535,14 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
 
     // ---- layer 1: H1 = tanh(X W1^T + b1); FVP: D1 = X V1^T + vb1; EVAL: D1 = tanh(X V1n^T + b1n)
     if constexpr (HCF) {
-      // the tangent's 4 tiles (units 16 cb, rows 16 rb), each as two chains: waves with
-      // (wave >> 1) & 1 == 0 the x.x / x.z chain (ca), the others the x.y / x.w chain (cb),
-      // which they leave in D1; then z = (ca + cb) + vb1 as the uncached pass forms it
+      // the tangent's 4 tiles (units 16 cb, rows 16 rb), each as four chains: waves with
+      // (wave >> 1) & 1 == 0 the x.x and x.z chains (ca + cc), the others the x.y and x.w chains
+      // (cb + cd), which they leave in D1; then z = ((ca + cc) + (cb + cd)) + vb1 as the uncached
+      // pass forms it
       if (NPG_PHASES & 1) {
         const int cb = wave & 1, rb = wave >> 2, ch = (wave >> 1) & 1;
         const float* xr = X + (rb * 16 + i) * XS + 4 * kq;
-        pf4 acc = {0.f, 0.f, 0.f, 0.f};
+        pf4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
         pf4 xq[2];
         xq[0] = *reinterpret_cast<const pf4*>(xr);
         xq[1] = *reinterpret_cast<const pf4*>(xr + 16 * min(1, JJ - 1));
@@ -551,7 +552,7 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
             const pf4 x = xq[jj & 1];
             if (jj + 2 < JJM) xq[jj & 1] = *reinterpret_cast<const pf4*>(xr + 16 * min(jj + 2, JJ - 1));
             acc = mma(x.x, wf[jj].x, acc);
-            acc = mma(x.z, wf[jj].z, acc);
+            acc2 = mma(x.z, wf[jj].z, acc2);
           }
         } else {
 #pragma unroll
@@ -559,9 +560,10 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
             const pf4 x = xq[jj & 1];
             if (jj + 2 < JJM) xq[jj & 1] = *reinterpret_cast<const pf4*>(xr + 16 * min(jj + 2, JJ - 1));
             acc = mma(x.y, wf[jj].y, acc);
-            acc = mma(x.w, wf[jj].w, acc);
+            acc2 = mma(x.w, wf[jj].w, acc2);
           }
         }
+        acc = acc + acc2;  // ca + cc, or cb + cd
         const int col = cb * 16 + i;
         if (ch) {
 #pragma unroll
@@ -579,16 +581,19 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
       }
     } else if ((NPG_PHASES & 1) && f1) {
       const float* xr[MI];
-      pf4 ca[MI], cb[MI], xq[MI][2];
+      pf4 ca[MI], cb[MI], cc[MI], cd[MI], xq[MI][2];
 #pragma unroll
       for (int m = 0; m < MI; ++m) {
         xr[m] = X + (((wave + NW * m) / (2 * NMAT)) * 16 + i) * XS + 4 * kq;
-        ca[m] = cb[m] = pf4{0.f, 0.f, 0.f, 0.f};
+        ca[m] = cb[m] = cc[m] = cd[m] = pf4{0.f, 0.f, 0.f, 0.f};
         // software-pipelined: step jj + 2's operand is read while step jj multiplies (clamped to
         // the last step: a read past JJ is never used)
         xq[m][0] = *reinterpret_cast<const pf4*>(xr[m]);
         xq[m][1] = *reinterpret_cast<const pf4*>(xr[m] + 16 * min(1, JJ - 1));
       }
+      // four fma chains (one per float of the float4 operand), ~S / 4 terms each: two chains of
+      // ~S / 2 left a cached activation 4.3 fp32 ulps of [0.5, 1) from the fp64 forward at S = 197
+      // (tests/test_gpu_npg_pass.py), four leave 2.9
 #pragma unroll
       for (int jj = 0; jj < JJM; ++jj) {  // no branch: a guarded MFMA costs accumulator copies
         pf4 x[MI];
@@ -601,8 +606,8 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
         for (int m = 0; m < MI; ++m) {
           ca[m] = mma(x[m].x, wf[jj].x, ca[m]);
           cb[m] = mma(x[m].y, wf[jj].y, cb[m]);
-          ca[m] = mma(x[m].z, wf[jj].z, ca[m]);
-          cb[m] = mma(x[m].w, wf[jj].w, cb[m]);
+          cc[m] = mma(x[m].z, wf[jj].z, cc[m]);
+          cd[m] = mma(x[m].w, wf[jj].w, cd[m]);
         }
       }
       const int col = cb1 * 16 + i;
@@ -613,7 +618,7 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = rb * 16 + 4 * kq + r;
-          const float z = (ca[m][r] + cb[m][r]) + bias;
+          const float z = ((ca[m][r] + cc[m][r]) + (cb[m][r] + cd[m][r])) + bias;
           if (!mat1) {
             const float hz = tanhf(z);
             H1[row * HS + col] = hz;
