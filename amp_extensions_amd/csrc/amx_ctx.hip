@@ -55,7 +55,7 @@ extern "C" amx_ctx* amx_create(int device, int S, int A, int n_models, int hidde
     return nullptr;
   }
   // amx_adv_whiten's per-block partials (allocated here: the launch stays graph-capturable)
-  if (hipMalloc((void**)&c->d_whiten_part, sizeof(double) * 3 * AMX_WHITEN_MAXB) != hipSuccess) {
+  if (hipMalloc((void**)&c->d_whiten_part, sizeof(double) * 4 * AMX_WHITEN_MAXB) != hipSuccess) {
     (void)hipFree(c->d_norm);
     free(c);
     amx::set_error("amx_create: hipMalloc of the whitening partials failed");

@@ -124,12 +124,20 @@ __global__ __launch_bounds__(256) void k_gae(Grid g, const uint8_t* __restrict__
 // (adv - mean) / (std + eps) over the grid's rows (np.mean / np.std, population std), in two
 // launches over the whole chip: the flat element range is cut into nb contiguous chunks of `ch`
 // elements (a multiple of 1024; a fixed partition: deterministic), and
-//   k_whiten_part: workgroup b reduces its chunk's count, sum and -- about its own mean, a second
-//     pass over the chunk (L1/L2-resident) -- sum of squared deviations M2_b (fixed order: thread
-//     strides, waves, then the 16 wave parts in order) into part[b];
-//   k_whiten_apply: every workgroup combines the nb parts in block order (Chan et al.'s pairwise
-//     update: mean = sum / n, M2 = sum_b M2_b + n_b (mean_b - mean)^2; the same bits in every
-//     workgroup), std = sqrt(M2 / n), and writes its chunk; workgroup 0 writes stats.
+//   k_whiten_part: workgroup b reduces its chunk's count n_b and mean m_b = sum_b / n_b and --
+//     about m_b as rounded, a second pass over the chunk (L1/L2-resident) -- the sum of squared
+//     deviations M2_b and the sum of deviations R_b (fixed order: thread strides, waves, then the
+//     16 wave parts in order) into part[b] = (n_b, m_b, M2_b, R_b);
+//   k_whiten_apply: every workgroup combines the nb parts in block order (the same bits in every
+//     workgroup): with a = the first non-empty chunk's m_b,
+//       mean = a + (sum_b R_b + n_b (m_b - a)) / n         (the sum of x - a, then one rounding)
+//       M2   = sum_b M2_b + 2 d_b R_b + n_b d_b^2,  d_b = m_b - mean
+//     (the squares about `mean` exactly, for the m_b and mean as computed), std = sqrt(M2 / n),
+//     and writes its chunk; workgroup 0 writes stats.
+//   R_b is what m_b's rounding left of the chunk's sum.  Chan et al.'s update takes it for 0; with
+//   |mean| >> std that costs std a relative n_b d_b ulp(mean) / M2 (2e-10 at mean / std = 1e9,
+//   where numpy's two passes are good to 1e-15), and a mean off by k ulp costs it (k ulp / std)^2
+//   / 2 more, so R_b is carried and the mean is summed as deviations from a.
 // (Round 4's one-workgroup form: 25 us for 40 960 advantages, profiles/r05c_npg_timeline.txt.)
 constexpr int WCH = 4096;  // elements per workgroup when the chunks fit AMX_WHITEN_MAXB workgroups
 
@@ -174,19 +182,22 @@ __global__ __launch_bounds__(1024) void k_whiten_part(Grid g, const double* __re
   const double sum = block_sum(s, red);
   const double n = block_sum(cnt, red);
   const double m = n > 0.0 ? sum / n : 0.0;
-  double q = 0.0;
+  double q = 0.0, dr = 0.0;
   for (long long i = c0 + threadIdx.x; i < c1; i += 1024) {
     long long r = 0;
     if (whiten_elem(g, flat, i, c1, r)) {
       const double d = adv[r] - m;
       q += d * d;
+      dr += d;
     }
   }
   const double m2 = block_sum(q, red);
+  const double res = block_sum(dr, red);
   if (threadIdx.x == 0) {
-    part[3 * blockIdx.x] = n;
-    part[3 * blockIdx.x + 1] = sum;
-    part[3 * blockIdx.x + 2] = m2;
+    part[4 * blockIdx.x] = n;
+    part[4 * blockIdx.x + 1] = m;
+    part[4 * blockIdx.x + 2] = m2;
+    part[4 * blockIdx.x + 3] = res;
   }
 }
 
@@ -196,19 +207,22 @@ __global__ __launch_bounds__(1024) void k_whiten_apply(Grid g, const double* __r
                                                        double* __restrict__ stats) {
   const long long total = (long long)g.T * g.L;
   const bool flat = g.T == 1 && g.len == nullptr && g.base == nullptr;
-  double n = 0.0, sum = 0.0;
+  double n = 0.0, dev = 0.0, a = 0.0;
+  bool have = false;
   for (int b = 0; b < nb; ++b) {  // every thread the same fixed order (broadcast loads)
-    n += part[3 * b];
-    sum += part[3 * b + 1];
-  }
-  const double mean = n > 0.0 ? sum / n : 0.0;
-  double m2 = 0.0;
-  for (int b = 0; b < nb; ++b) {
-    const double nbk = part[3 * b];
+    const double nbk = part[4 * b];
     if (nbk > 0.0) {
-      const double d = part[3 * b + 1] / nbk - mean;
-      m2 += part[3 * b + 2] + nbk * d * d;
+      if (!have) a = part[4 * b + 1];  // the shift: the first non-empty chunk's mean
+      have = true;
+      n += nbk;
+      dev += part[4 * b + 3] + nbk * (part[4 * b + 1] - a);
     }
+  }
+  const double mean = n > 0.0 ? a + dev / n : 0.0;
+  double m2 = 0.0;
+  for (int b = 0; b < nb; ++b) {  // an empty chunk's part is (0, 0, 0, 0) and adds 0
+    const double nbk = part[4 * b], d = part[4 * b + 1] - mean;
+    m2 += part[4 * b + 2] + (2.0 * d * part[4 * b + 3] + nbk * d * d);
   }
   const double sd = n > 0.0 ? sqrt(m2 / n) : 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 0 && stats) {
