@@ -20,7 +20,7 @@ __all__ = [
     "DevicePolicy",
     "TerminationConfig", "SimEnv", "BatchedSimEnv", "sample_points", "DeviceMLPBaseline", "process_samples",
     "DeviceNPG", "AgentReplayBuffer", "BC", "DeviceBC", "plan_bc_batches",
-    "PPO", "DevicePPO", "NPG", "TimeWarper",
+    "PPO", "DevicePPO", "NPG", "TimeWarper", "PlainDynamicsEnsemble", "dynamics_ensemble",
 ]
 
 
@@ -55,6 +55,9 @@ def __getattr__(name):
     if name in ("PPO", "DevicePPO"):
         from . import ppo
         return getattr(ppo, name)
+    if name in ("PlainDynamicsEnsemble", "dynamics_ensemble"):
+        from . import ensemble
+        return getattr(ensemble, name)
     if name == "TimeWarper":
         from .dtw import TimeWarper
         return TimeWarper

@@ -43,6 +43,7 @@ RFF_PART_ROWS = 32  # AMX_RFF_PART_ROWS: rows per fp64 column partial of the RFF
 # name -> (restype, argtypes); must match include/amx_hip.h exactly.
 SIGNATURES = {
     "amx_create": (vp, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "amx_create_ex": (vp, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "amx_destroy": (c_int, [vp]),
     "amx_last_error": (C.c_char_p, []),
     "amx_abi_version": (c_int, []),
@@ -71,6 +72,10 @@ SIGNATURES = {
                                      vp, c_ll, vp, c_int, c_ll, c_int, c_int, vp, c_ll, c_int, vp, c_int, vp]),
     "amx_gemm_out_unnorm_h3": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_ll, vp, c_ll,
                                        vp, c_ll, vp, c_int, c_ll, vp, c_ll, c_int, c_int, vp]),
+    "amx_gemm_bias_act_h3_win": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_ll, vp, c_ll,
+                                         vp, c_ll, vp, c_int, c_ll, c_int, c_int, vp, c_ll, c_int, vp, c_int, vp]),
+    "amx_gemm_out_unnorm_h3_win": (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, c_ll, vp, c_ll, vp, c_ll,
+                                           vp, c_ll, vp, c_int, c_ll, vp, c_ll, c_int, vp]),
     "amx_set_motion": (c_int, [vp, vp, c_ll]),
     "amx_motion_duration": (c_dbl, [vp]),
     "amx_motion_states": (c_int, [vp, vp, c_int, c_int, vp, c_ll, vp]),
@@ -182,6 +187,7 @@ AMX_ROW_TILE = 128
 AMX_K_TILE = 32
 AMX_SHAPE_SPHERE, AMX_SHAPE_CAPSULE, AMX_SHAPE_BOX = 0, 1, 2
 AMX_ACT_NONE, AMX_ACT_RELU = 0, 1
+AMX_CONNECT_DENSE, AMX_CONNECT_PLAIN = 0, 1
 AMX_IN_F64, AMX_IN_F32 = 0, 1
 AMX_DISC_LEAST_SQUARES, AMX_DISC_LOG_LIKELIHOOD = 0, 1
 AMX_EFIT_ADAM, AMX_EFIT_SGD = 0, 1

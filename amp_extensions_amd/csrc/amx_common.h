@@ -33,6 +33,7 @@ struct amx_ctx {
   int n_cus;               // compute units of the device (tile selection: workgroups resident at once)
   int S, A, M, H, L, F;
   int k0_pad, ldk, n_out_pad, k_rff_pad;
+  int plain;               // amx_create_ex: AMX_CONNECT_PLAIN (layer i reads layer i-1's window only)
   // device copies of the normalizers: mu_s, sd_s (S), mu_a, sd_a (A), mu_d, sd_d (S)
   float* d_norm;
   int have_norm;

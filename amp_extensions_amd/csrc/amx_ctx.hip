@@ -20,6 +20,19 @@ extern "C" int amx_abi_version(void) { return AMX_ABI_VERSION; }
 
 extern "C" amx_ctx* amx_create(int device, int S, int A, int n_models, int hidden, int n_hidden,
                                int feat_dim) {
+  return amx_create_ex(device, S, A, n_models, hidden, n_hidden, feat_dim, AMX_CONNECT_DENSE);
+}
+
+extern "C" amx_ctx* amx_create_ex(int device, int S, int A, int n_models, int hidden, int n_hidden,
+                                  int feat_dim, int connect) {
+  if (connect != AMX_CONNECT_DENSE && connect != AMX_CONNECT_PLAIN) {
+    amx::set_error("amx_create_ex: connect=%d (AMX_CONNECT_DENSE or AMX_CONNECT_PLAIN)", connect);
+    return nullptr;
+  }
+  if (connect == AMX_CONNECT_PLAIN && n_hidden < 1) {
+    amx::set_error("amx_create_ex: a plain network needs at least one hidden layer, got %d", n_hidden);
+    return nullptr;
+  }
   if (S <= 0 || A <= 0 || n_models <= 0 || n_models > AMX_MAX_MODELS || hidden <= 0 ||
       hidden % 128 != 0 || n_hidden < 0 || feat_dim <= 0 || feat_dim % 128 != 0) {
     amx::set_error("amx_create: bad dims S=%d A=%d M=%d H=%d L=%d F=%d (H, F must be multiples of 128, M <= %d)",
@@ -45,6 +58,7 @@ extern "C" amx_ctx* amx_create(int device, int S, int A, int n_models, int hidde
   c->H = hidden;
   c->L = n_hidden;
   c->F = feat_dim;
+  c->plain = connect == AMX_CONNECT_PLAIN;
   c->k0_pad = amx::round_up(S + A, AMX_K_TILE);
   c->ldk = c->k0_pad + n_hidden * hidden;
   c->n_out_pad = amx::round_up(S, AMX_ROW_TILE);

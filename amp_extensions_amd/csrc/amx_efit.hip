@@ -11,6 +11,9 @@
 //     k_efit_wgrad  gW_i = dZ_i^T act, gb_i = column sums of dZ_i
 //     k_efit_dgrad  dact[:, hidden slices < i] (+)= dZ_i W_i; the tiles of slice i - 1, final
 //                   after this launch, write dZ_{i-1} = dact * (act > 0)
+//   A plain context (AMX_CONNECT_PLAIN): layer i >= 1 has K = Hp and reads the window of layer
+//   i - 1 alone, so its weight gradient is taken against that window and its k_efit_dgrad launch
+//   covers that one slice, final at once (no accumulation, dact unused).
 //   k_optim_sumsq   per-workgroup partial sums of g^2 (grad_clip > 0; amx_optim.hip)
 //   k_efit_prep     clip_grad_norm_'s coefficient, the step count and Adam's bias corrections
 //   k_optim_update  torch.optim.Adam / SGD(nesterov=True) on every padded tensor (amx_optim.hip)
@@ -32,6 +35,9 @@ constexpr int EF_CONST = amx::STEP_CONST_FLOATS;  // floats of a member's step c
 
 struct Plan {
   int M, L, Hp, k0, ldk, NO, S, A;
+  int plain;                     // layer i >= 1 reads the window of layer i - 1 only
+  int K[EF_MAX_LAYERS];          // columns of W_i
+  int in0[EF_MAX_LAYERS];        // first column of the activation row that layer i reads
   long long P;                   // floats of a member's flat gradient
   long long offW[EF_MAX_LAYERS], offB[EF_MAX_LAYERS];
 };
@@ -42,9 +48,13 @@ int make_plan(const char* fn, const amx_ctx* c, Plan* p) {
                 EF_MAX_LAYERS - 1);
   p->M = c->M; p->L = c->L; p->Hp = c->H; p->k0 = c->k0_pad; p->ldk = c->ldk; p->NO = c->n_out_pad;
   p->S = c->S; p->A = c->A;
+  p->plain = c->plain;
   long long o = 0;
   for (int i = 0; i <= c->L; ++i) {
-    const long long N = i == c->L ? c->n_out_pad : c->H, K = i == c->L ? c->ldk : c->k0_pad + (long long)i * c->H;
+    const long long N = i == c->L ? c->n_out_pad : c->H;
+    p->K[i] = (c->plain && i > 0) ? c->H : (i == c->L ? c->ldk : c->k0_pad + i * c->H);
+    p->in0[i] = (c->plain && i > 0) ? c->k0_pad + (i - 1) * c->H : 0;
+    const long long K = p->K[i];
     p->offW[i] = o;
     o += N * K;
     p->offB[i] = o;
@@ -323,13 +333,13 @@ extern "C" int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int
   const bool small = (long long)M * (Bt / 128) * (Hp / 128) < ctx->n_cus;
   const auto fwd = small ? amx_gemm_bias_act_t64 : amx_gemm_bias_act;
   for (int i = 0; i < L; ++i) {
-    const int K = k0 + i * Hp;
-    rc = fwd(ctx, M, Bt, Hp, K, act, ldk, sA, W[i], K, (long long)Hp * K, b[i], Hp, act, ldk, sA, K,
-                           AMX_ACT_RELU, stream);
+    const int K = p.K[i];
+    rc = fwd(ctx, M, Bt, Hp, K, act + p.in0[i], ldk, sA, W[i], K, (long long)Hp * K, b[i], Hp, act, ldk, sA,
+                           k0 + i * Hp, AMX_ACT_RELU, stream);
     if (rc) return rc;
   }
-  rc = fwd(ctx, M, Bt, NO, ldk, act, ldk, sA, W[L], ldk, (long long)NO * ldk, b[L], NO, pred, NO, sO, 0,
-                         AMX_ACT_NONE, stream);
+  rc = fwd(ctx, M, Bt, NO, p.K[L], act + p.in0[L], ldk, sA, W[L], p.K[L], (long long)NO * p.K[L], b[L], NO, pred, NO,
+                         sO, 0, AMX_ACT_NONE, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(k_efit_loss, dim3(M), dim3(1024), 0, st, n_b, Bt, p.S, NO, pred, target, dzL, loss, strideLoss);
   AMX_CHECK_LAUNCH();
@@ -340,14 +350,25 @@ extern "C" int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int
   int ldz = NO;
   long long sZ = sO;
   for (int i = L; i >= 0; --i) {
-    const int N = i == L ? NO : Hp, K = i == L ? ldk : k0 + i * Hp;
-    hipLaunchKernelGGL(k_efit_wgrad, dim3((K + 63) / 64, N / 64, M), dim3(256), 0, st, rows16, K, dz, ldz, sZ, act, ldk,
-                       sA, grad + p.offW[i], grad + p.offB[i], p.P);
+    const int N = i == L ? NO : Hp, K = p.K[i];
+    hipLaunchKernelGGL(k_efit_wgrad, dim3((K + 63) / 64, N / 64, M), dim3(256), 0, st, rows16, K, dz, ldz, sZ,
+                       act + p.in0[i], ldk, sA, grad + p.offW[i], grad + p.offB[i], p.P);
     AMX_CHECK_LAUNCH();
     if (i == 0) break;
     // the reduction of the output layer stops at the last valid column's 16-block (dzL is zero past S)
     const int Nred = i == L ? amx::round_up(p.S, 16) : Hp;
     float* out = dzb[i & 1];
+    if (p.plain) {
+      // dZ_{i-1} = (dZ_i W_i) * (h_{i-1} > 0): W_i's Hp columns are that one window, whose ReLU
+      // mask is read at act + in0[i] (k0 = 0, final_c0 = 0: every tile is final, dact untouched)
+      hipLaunchKernelGGL(k_efit_dgrad, dim3(Hp / 64, rows64 / 64, M), dim3(256), 0, st, Nred, 0, 0, 0, dz, ldz, sZ, W[i],
+                         K, (long long)N * K, act + p.in0[i], ldk, sA, dact, L * Hp, sD, out, Hp, sH);
+      AMX_CHECK_LAUNCH();
+      dz = out;
+      ldz = Hp;
+      sZ = sH;
+      continue;
+    }
     hipLaunchKernelGGL(k_efit_dgrad, dim3(i * Hp / 64, rows64 / 64, M), dim3(256), 0, st, Nred, k0, i == L ? 0 : 1,
                        (i - 1) * Hp, dz, ldz, sZ, W[i], K, (long long)N * K, act, ldk, sA, dact, L * Hp, sD, out, Hp,
                        sH);
@@ -368,7 +389,7 @@ extern "C" int amx_efit_step(amx_ctx* ctx, int train, int n_b, int Bt, const int
   amx::TensorList T = {};
   T.n = 2 * (L + 1);
   for (int i = 0; i <= L; ++i) {
-    const long long N = i == L ? NO : Hp, K = i == L ? ldk : k0 + (long long)i * Hp;
+    const long long N = i == L ? NO : Hp, K = p.K[i];
     T.w[2 * i] = W[i]; T.stride[2 * i] = N * K; T.off[2 * i] = p.offW[i];
     T.w[2 * i + 1] = b[i]; T.stride[2 * i + 1] = N; T.off[2 * i + 1] = p.offB[i];
   }

@@ -1745,23 +1745,19 @@ static bool small_hidden(const amx_ctx* ctx, int groups, int rows, int N) {
   return N % 256 == 0 && rows % 128 == 0 && 2LL * (rows / 128) * (N / 256) * groups < ctx->n_cus;
 }
 
-extern "C" int amx_gemm_bias_act_h3(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
-                                    long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
-                                    long long strideWexp, const float* bias, long long strideBias, float* C, int ldc,
-                                    long long strideC, int col_off, int act, const int* row_exp,
-                                    long long strideRexp, int rexp_slots, int* row_exp_out, int k_shared,
-                                    void* stream) {
-  AMX_CHECK_ARG(ctx, "amx_gemm_bias_act_h3: null ctx");
-  int rc = check_h3("amx_gemm_bias_act_h3", groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, rexp_slots,
-                    k_shared);
-  if (rc) return rc;
-  AMX_CHECK_ARG(N > 0 && N % 128 == 0, "amx_gemm_bias_act_h3: N=%d must be a multiple of 128", N);
-  AMX_CHECK_ARG(strideW2 >= 2LL * K * N || groups == 1, "amx_gemm_bias_act_h3: strideW2=%lld < 2*K*N", strideW2);
-  AMX_CHECK_ARG(bias && C, "amx_gemm_bias_act_h3: null bias/C");
-  AMX_CHECK_ARG(col_off >= 0 && col_off + N <= ldc, "amx_gemm_bias_act_h3: col_off=%d N=%d ldc=%d", col_off, N, ldc);
-  AMX_CHECK_ARG(act == AMX_ACT_NONE || act == AMX_ACT_RELU, "amx_gemm_bias_act_h3: act=%d", act);
-  AMX_CHECK_ARG(strideRexp >= (long long)rexp_slots * rows || groups == 1, "amx_gemm_bias_act_h3: strideRexp=%lld",
-                strideRexp);
+// The hidden layer behind amx_gemm_bias_act_h3 and its windowed form: row_exp = the first slot
+// read, first_layer = the launch that stamps the timer's start.
+static int bias_act_h3(const char* fn, amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
+                       long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
+                       long long strideWexp, const float* bias, long long strideBias, float* C, int ldc,
+                       long long strideC, int col_off, int act, const int* row_exp, long long strideRexp,
+                       int rexp_slots, int* row_exp_out, int k_shared, int first_layer, void* stream) {
+  AMX_CHECK_ARG(N > 0 && N % 128 == 0, "%s: N=%d must be a multiple of 128", fn, N);
+  AMX_CHECK_ARG(strideW2 >= 2LL * K * N || groups == 1, "%s: strideW2=%lld < 2*K*N", fn, strideW2);
+  AMX_CHECK_ARG(bias && C, "%s: null bias/C", fn);
+  AMX_CHECK_ARG(col_off >= 0 && col_off + N <= ldc, "%s: col_off=%d N=%d ldc=%d", fn, col_off, N, ldc);
+  AMX_CHECK_ARG(act == AMX_ACT_NONE || act == AMX_ACT_RELU, "%s: act=%d", fn, act);
+  AMX_CHECK_ARG(strideRexp >= (long long)rexp_slots * rows || groups == 1, "%s: strideRexp=%lld", fn, strideRexp);
   GemmArgs a = {};
   a.A = A; a.strideA = strideA; a.lda = lda;
   a.W2 = W2; a.strideW2 = strideW2; a.w_exp = w_exp; a.strideWexp = strideWexp;
@@ -1770,7 +1766,7 @@ extern "C" int amx_gemm_bias_act_h3(amx_ctx* ctx, int groups, int rows, int N, i
   a.rows = rows; a.N = N; a.K = K; a.act = act; a.groups = groups;
   a.row_exp = row_exp; a.strideRexp = strideRexp; a.rexp_slots = rexp_slots; a.row_exp_out = row_exp_out;
   a.k_shared = k_shared;
-  if (ctx->gemm_timer && rexp_slots == 1) { a.timer = ctx->gemm_timer; a.timer_role = 1; }
+  if (ctx->gemm_timer && first_layer) { a.timer = ctx->gemm_timer; a.timer_role = 1; }
   const hipStream_t s = (hipStream_t)stream;
   if (rows % 256 == 0 && N % 256 == 0 && K % 32 == 0 &&
       (long long)(rows / 256) * (N / 256) * groups >= resident_wgs(ctx, H256::LDS, H256::NT, 2))
@@ -1801,6 +1797,47 @@ extern "C" int amx_gemm_bias_act_h3(amx_ctx* ctx, int groups, int rows, int N, i
   return launch_h3<EPI_BIAS_ACT, H128>(a, s);
 }
 
+extern "C" int amx_gemm_bias_act_h3(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
+                                    long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
+                                    long long strideWexp, const float* bias, long long strideBias, float* C, int ldc,
+                                    long long strideC, int col_off, int act, const int* row_exp,
+                                    long long strideRexp, int rexp_slots, int* row_exp_out, int k_shared,
+                                    void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_gemm_bias_act_h3: null ctx");
+  int rc = check_h3("amx_gemm_bias_act_h3", groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, rexp_slots,
+                    k_shared);
+  if (rc) return rc;
+  return bias_act_h3("amx_gemm_bias_act_h3", ctx, groups, rows, N, K, A, lda, strideA, W2, strideW2, w_exp, strideWexp,
+                     bias, strideBias, C, ldc, strideC, col_off, act, row_exp, strideRexp, rexp_slots, row_exp_out,
+                     k_shared, rexp_slots == 1, stream);
+}
+
+// the windowed forms' exponent arguments: one slot, rexp_first, of a table whose slot stride is `rows`
+static int check_win(const char* fn, int groups, int rows, long long strideRexp, int rexp_first, int first_layer) {
+  AMX_CHECK_ARG(rexp_first >= 0 && rexp_first < 64, "%s: rexp_first=%d", fn, rexp_first);
+  AMX_CHECK_ARG(strideRexp >= (long long)(rexp_first + 1) * rows || groups == 1, "%s: strideRexp=%lld (slot %d)", fn,
+                strideRexp, rexp_first);
+  AMX_CHECK_ARG(first_layer == 0 || first_layer == 1, "%s: first_layer=%d", fn, first_layer);
+  return AMX_OK;
+}
+
+extern "C" int amx_gemm_bias_act_h3_win(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
+                                        long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
+                                        long long strideWexp, const float* bias, long long strideBias, float* C,
+                                        int ldc, long long strideC, int col_off, int act, const int* row_exp,
+                                        long long strideRexp, int rexp_first, int* row_exp_out, int first_layer,
+                                        void* stream) {
+  const char* fn = "amx_gemm_bias_act_h3_win";
+  AMX_CHECK_ARG(ctx, "%s: null ctx", fn);
+  int rc = check_h3(fn, groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, 1, 0);
+  if (rc) return rc;
+  if ((rc = check_win(fn, groups, rows, strideRexp, rexp_first, first_layer))) return rc;
+  // the tiles take the slot stride to be their launch's rows: the window's slot is the table's base
+  return bias_act_h3(fn, ctx, groups, rows, N, K, A, lda, strideA, W2, strideW2, w_exp, strideWexp, bias, strideBias,
+                     C, ldc, strideC, col_off, act, row_exp + (long long)rexp_first * rows, strideRexp, 1,
+                     row_exp_out, 0, first_layer, stream);
+}
+
 // Output-layer tiles (128 x 224, S <= 224) of a stream-K launch for `rows` padded lanes x
 // `groups` members when the tiles are fewer than the CUs but at least half as many (4096-7168
 // lanes x 4 members: 128-224 tiles): one workgroup per CU, the tiles' K-tiles dealt out evenly,
@@ -1828,17 +1865,14 @@ static bool small_out(const amx_ctx* ctx, int groups, int rows) {
   return n32 > 128 && n32 <= 224 && rows % 128 == 0 && 2LL * (rows / 128) * groups < ctx->n_cus;
 }
 
-extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_valid, int K, const float* A,
-                                      int lda, long long strideA, const uint16_t* W2, long long strideW2,
-                                      const int* w_exp, long long strideWexp, const float* bias, long long strideBias,
-                                      float* preds, int ldp, long long strideP, const int* row_exp,
-                                      long long strideRexp, int rexp_slots, int k_shared, void* stream) {
-  AMX_CHECK_ARG(ctx && ctx->have_norm, "amx_gemm_out_unnorm_h3: context has no normalizers");
-  int rc = check_h3("amx_gemm_out_unnorm_h3", groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, rexp_slots,
-                    k_shared);
-  if (rc) return rc;
-  AMX_CHECK_ARG(n_valid == ctx->S, "amx_gemm_out_unnorm_h3: n_valid=%d must equal S=%d", n_valid, ctx->S);
-  AMX_CHECK_ARG(bias && preds && ldp >= n_valid, "amx_gemm_out_unnorm_h3: null bias/preds or ldp=%d", ldp);
+// The output layer behind amx_gemm_out_unnorm_h3 and its windowed form (row_exp = the first slot read).
+static int out_unnorm_h3(const char* fn, amx_ctx* ctx, int groups, int rows, int n_valid, int K, const float* A,
+                         int lda, long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
+                         long long strideWexp, const float* bias, long long strideBias, float* preds, int ldp,
+                         long long strideP, const int* row_exp, long long strideRexp, int rexp_slots, int k_shared,
+                         void* stream) {
+  AMX_CHECK_ARG(n_valid == ctx->S, "%s: n_valid=%d must equal S=%d", fn, n_valid, ctx->S);
+  AMX_CHECK_ARG(bias && preds && ldp >= n_valid, "%s: null bias/preds or ldp=%d", fn, ldp);
   GemmArgs a = {};
   a.A = A; a.strideA = strideA; a.lda = lda;
   a.W2 = W2; a.strideW2 = strideW2; a.w_exp = w_exp; a.strideWexp = strideWexp;
@@ -1860,7 +1894,7 @@ extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_
   const bool row_tiles = K % 32 == 0 && (rb == 128 || rb == 160 || rb == 192 || rb == 224);
   if (n32 > 128 && n32 <= 224) {
     a.N = 224;
-    AMX_CHECK_ARG(strideW2 >= 2LL * K * 224 || groups == 1, "amx_gemm_out_unnorm_h3: strideW2=%lld", strideW2);
+    AMX_CHECK_ARG(strideW2 >= 2LL * K * 224 || groups == 1, "%s: strideW2=%lld", fn, strideW2);
     if (K % 32 != 0) return launch_h3<EPI_UNNORM, H128x224k16>(a, s);
     if (rows % 80 == 0 && (long long)groups * (rows / 80) == ctx->n_cus) return launch_h3<EPI_UNNORM, H80x224>(a, s);
     // lane counts whose 128 x 224 tiles (14 waves) are fewer than the CUs (4096-7168 lanes x 4
@@ -1892,7 +1926,7 @@ extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_
     return launch_h3<EPI_UNNORM, H128x224>(a, s);
   }
   a.N = amx::round_up(n_valid, 128);
-  AMX_CHECK_ARG(strideW2 >= 2LL * K * a.N || groups == 1, "amx_gemm_out_unnorm_h3: strideW2=%lld", strideW2);
+  AMX_CHECK_ARG(strideW2 >= 2LL * K * a.N || groups == 1, "%s: strideW2=%lld", fn, strideW2);
   if (K % 32 == 0) {
     if (a.N == 256 && row_tiles) {
       switch (rb) {
@@ -1906,6 +1940,35 @@ extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_
     return launch_h3<EPI_UNNORM, H128k32>(a, s);
   }
   return launch_h3<EPI_UNNORM, H128>(a, s);
+}
+
+extern "C" int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_valid, int K, const float* A,
+                                      int lda, long long strideA, const uint16_t* W2, long long strideW2,
+                                      const int* w_exp, long long strideWexp, const float* bias, long long strideBias,
+                                      float* preds, int ldp, long long strideP, const int* row_exp,
+                                      long long strideRexp, int rexp_slots, int k_shared, void* stream) {
+  AMX_CHECK_ARG(ctx && ctx->have_norm, "amx_gemm_out_unnorm_h3: context has no normalizers");
+  int rc = check_h3("amx_gemm_out_unnorm_h3", groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, rexp_slots,
+                    k_shared);
+  if (rc) return rc;
+  return out_unnorm_h3("amx_gemm_out_unnorm_h3", ctx, groups, rows, n_valid, K, A, lda, strideA, W2, strideW2, w_exp,
+                       strideWexp, bias, strideBias, preds, ldp, strideP, row_exp, strideRexp, rexp_slots, k_shared,
+                       stream);
+}
+
+extern "C" int amx_gemm_out_unnorm_h3_win(amx_ctx* ctx, int groups, int rows, int n_valid, int K, const float* A,
+                                          int lda, long long strideA, const uint16_t* W2, long long strideW2,
+                                          const int* w_exp, long long strideWexp, const float* bias,
+                                          long long strideBias, float* preds, int ldp, long long strideP,
+                                          const int* row_exp, long long strideRexp, int rexp_first, void* stream) {
+  const char* fn = "amx_gemm_out_unnorm_h3_win";
+  AMX_CHECK_ARG(ctx && ctx->have_norm, "%s: context has no normalizers", fn);
+  int rc = check_h3(fn, groups, rows, K, A, lda, W2, strideW2, w_exp, row_exp, 1, 0);
+  if (rc) return rc;
+  if ((rc = check_win(fn, groups, rows, strideRexp, rexp_first, 0))) return rc;
+  return out_unnorm_h3(fn, ctx, groups, rows, n_valid, K, A, lda, strideA, W2, strideW2, w_exp, strideWexp, bias,
+                       strideBias, preds, ldp, strideP, row_exp + (long long)rexp_first * rows, strideRexp, 1, 0,
+                       stream);
 }
 
 // The two f16x3 feature layers (EPI_RFF, EPI_MLPF): one argument check and one tile dispatch.
@@ -1983,16 +2046,18 @@ extern "C" long long amx_split_workspace_floats(const amx_ctx* ctx, int groups, 
     nc = tiles > nc ? tiles : nc;
   };
   int nwg = 0, ksplit = 0;
-  const int ldk = ctx->k0_pad + ctx->L * ctx->H;
+  // the output layer's K: the whole activation row, or a plain network's last hidden window
+  const int k_out = ctx->plain ? ctx->H : ctx->k0_pad + ctx->L * ctx->H;
   const int to = streamk_tiles(ctx, groups, rows, &nwg, &ksplit);
   need(to, ksplit, 128, 224);
   if (small_out(ctx, groups, rows)) {
-    const int t = small_plan(ctx, groups, rows, 224, ldk, HS32::BN, &nwg, &ksplit);
+    const int t = small_plan(ctx, groups, rows, 224, k_out, HS32::BN, &nwg, &ksplit);
     need(t, ksplit, HS32::BM, HS32::BN);
   }
   if (small_hidden(ctx, groups, rows, ctx->H)) {
     for (int i = 0; i < ctx->L; ++i) {  // every hidden layer's K (segments per tile depend on it)
-      const int t = small_plan(ctx, groups, rows, ctx->H, ctx->k0_pad + i * ctx->H, HS64::BN, &nwg, &ksplit);
+      const int k_i = (ctx->plain && i > 0) ? ctx->H : ctx->k0_pad + i * ctx->H;
+      const int t = small_plan(ctx, groups, rows, ctx->H, k_i, HS64::BN, &nwg, &ksplit);
       need(t, ksplit, HS64::BM, HS64::BN);
     }
   }

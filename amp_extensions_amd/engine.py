@@ -9,6 +9,11 @@ Layout in HBM (all fp32 unless noted; B_pad = round_up(B, 128)):
   preds [M][B_pad][S]        un-normalised state deltas of every member
 Hidden widths that are not multiples of 128 are zero-padded (ReLU(0) = 0 keeps the pad
 inert), so any BasicMLP config runs on the same 128x128 MFMA tiles.
+
+A plain (dense_connect=False) context keeps those activation rows; only the weights differ:
+  W_i   [M][Hp][Hp]          i >= 1: reads the K window [k0_pad + (i-1)*Hp, k0_pad + i*Hp)
+  W_out [M][n_out_pad][Hp]   reads the last hidden window
+(W_0 [M][Hp][k0_pad] as above; DeviceEnsemble.layer_windows).
 """
 from __future__ import annotations
 
@@ -18,7 +23,7 @@ import torch
 
 from . import _native as N
 from .humanoid import TerminationConfig
-from .optstate import ensemble_layout, pack_state
+from .optstate import ensemble_layout, pack_state, plain_ensemble_layout
 
 
 def round_up(x: int, m: int) -> int:
@@ -29,7 +34,8 @@ class AmxContext:
     """One amx_ctx per device (include/amx_hip.h)."""
 
     def __init__(self, S: int, A: int, n_models: int = 4, hidden: int = 512, n_hidden: int = 4,
-                 feat_dim: int = 512, device: torch.device | str | int = "cuda"):
+                 feat_dim: int = 512, device: torch.device | str | int = "cuda", dense_connect: bool = True):
+        """dense_connect=False: a plain BasicMLP (amx_create_ex with AMX_CONNECT_PLAIN)."""
         self.lib = N.load()
         self.device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
         if self.device.type != "cuda":
@@ -40,8 +46,12 @@ class AmxContext:
         self.Hp = round_up(hidden, 128)
         self.L = n_hidden
         self.F = round_up(feat_dim, 128)
+        self.dense_connect = bool(dense_connect)
         with torch.cuda.device(idx):
-            h = self.lib.amx_create(idx, S, A, n_models, self.Hp, n_hidden, self.F)
+            if self.dense_connect:
+                h = self.lib.amx_create(idx, S, A, n_models, self.Hp, n_hidden, self.F)
+            else:
+                h = self.lib.amx_create_ex(idx, S, A, n_models, self.Hp, n_hidden, self.F, N.AMX_CONNECT_PLAIN)
         if not h:
             raise N.AmxNativeError("amx_create failed: " + self.lib.amx_last_error().decode())
         self.h = h
@@ -151,7 +161,8 @@ def _check_dev(t: torch.Tensor, dtype, name: str, device) -> None:
 
 
 class DeviceEnsemble:
-    """The dense-connect BasicMLP ensemble resident in HBM (milo/milo/dynamics.py:19-233).
+    """The BasicMLP ensemble resident in HBM (milo/milo/dynamics.py:19-233), dense-connect or
+    plain as its context is (AmxContext.dense_connect).
 
     `weights[m]` = [(W0, b0), ..., (WL, bL)] in nn.Linear layout (W [out, in]); `norms` =
     the 6 transformation vectors of AmpDataset.get_transformations (datasets.py:23-43).
@@ -178,7 +189,13 @@ class DeviceEnsemble:
         self.hidden = hidden
         if round_up(hidden, 128) != Hp or len(weights[0]) != L + 1:
             raise ValueError("weights do not match the context's (hidden, n_hidden)")
-        self.layout = ensemble_layout(ctx.S, ctx.A, hidden, L, ctx.k0_pad, Hp, ctx.ldk, ctx.n_out_pad)  # per member
+        self.plain = not ctx.dense_connect
+        if self.plain:
+            if L < 1:
+                raise ValueError("a plain ensemble needs at least one hidden layer")
+            self.layout = plain_ensemble_layout(ctx.S, ctx.A, hidden, L, ctx.k0_pad, Hp, ctx.n_out_pad)
+        else:
+            self.layout = ensemble_layout(ctx.S, ctx.A, hidden, L, ctx.k0_pad, Hp, ctx.ldk, ctx.n_out_pad)  # per member
         self.W = self.b = self.W3 = self.W2 = self.wexp = None
         self.set_weights(weights)
         ctx.set_normalizers(norms)
@@ -229,6 +246,15 @@ class DeviceEnsemble:
     @property
     def num_models(self) -> int:
         return self.ctx.M
+
+    def layer_windows(self):
+        """(first column, K) of the activation row that layer i = 0 .. L reads: the leading
+        k0_pad + i*Hp columns (the whole row for the output layer) of a dense-connect net, the
+        previous layer's Hp columns of a plain one."""
+        c = self.ctx
+        if not self.plain:
+            return [(0, c.k0_pad + i * c.Hp) for i in range(c.L + 1)]
+        return [(0, c.k0_pad)] + [(c.k0_pad + (i - 1) * c.Hp, c.Hp) for i in range(1, c.L + 1)]
 
     def workspace(self, B: int):
         """Activation + prediction buffers for B lanes (cached per B_pad).  B_pad = round_up(B, 128),
@@ -293,6 +319,9 @@ class DeviceEnsemble:
         if not x0_ready:  # x0 once per lane + slot 0 of its member block's exponents (slot stride Bq)
             N.check(c.lib.amx_assemble_input_rexp(c.h, ob.data_ptr(), act.data_ptr(), dt, buf.data_ptr(), 0, c.ldk, B,
                                                   rexp.data_ptr(), sR, Bq, self.n_slots, s), "amx_assemble_input_rexp")
+        if self.plain:
+            self._mlp_h3_plain(buf, preds, Bq, s, rexp, sA, sR, Bq * c.S, 0)
+            return preds
         for i in range(L):
             K = c.k0_pad + i * c.Hp
             N.check(c.lib.amx_gemm_bias_act_h3(c.h, c.M, Bq, c.Hp, K, buf.data_ptr(), c.ldk, sA, self.W2[i].data_ptr(),
@@ -304,6 +333,29 @@ class DeviceEnsemble:
                                              c.n_out_pad, self.b[L].data_ptr(), c.n_out_pad, preds.data_ptr(), c.S,
                                              Bq * c.S, rexp.data_ptr(), sR, L + 1, 0, s), "amx_gemm_out_unnorm_h3")
         return preds
+
+    def _mlp_h3_plain(self, buf, preds, rows, s, rexp, sA, sR, sP, k_shared):
+        """The f16x3 forward of a plain net over `rows` rows per member: layer 0 as the dense
+        one's (x0, slot 0, shared below k_shared), then each layer on the window and the one
+        exponent slot of the layer before it (amx_gemm_*_h3_win)."""
+        c = self.ctx
+        L, Hp, k0 = c.L, c.Hp, c.k0_pad
+        N.check(c.lib.amx_gemm_bias_act_h3(c.h, c.M, rows, Hp, k0, buf.data_ptr(), c.ldk, sA, self.W2[0].data_ptr(),
+                                           Hp * 2 * k0, self.wexp[0].data_ptr(), Hp, self.b[0].data_ptr(), Hp,
+                                           buf.data_ptr(), c.ldk, sA, k0, N.AMX_ACT_RELU, rexp.data_ptr(), sR, 1,
+                                           rexp[0, 1].data_ptr(), k_shared, s), "amx_gemm_bias_act_h3")
+        for i in range(1, L):
+            a0 = buf.data_ptr() + 4 * (k0 + (i - 1) * Hp)
+            N.check(c.lib.amx_gemm_bias_act_h3_win(c.h, c.M, rows, Hp, Hp, a0, c.ldk, sA, self.W2[i].data_ptr(),
+                                                   Hp * 2 * Hp, self.wexp[i].data_ptr(), Hp, self.b[i].data_ptr(), Hp,
+                                                   buf.data_ptr(), c.ldk, sA, k0 + i * Hp, N.AMX_ACT_RELU,
+                                                   rexp.data_ptr(), sR, i, rexp[0, i + 1].data_ptr(), 0, s),
+                    "amx_gemm_bias_act_h3_win")
+        a0 = buf.data_ptr() + 4 * (k0 + (L - 1) * Hp)
+        N.check(c.lib.amx_gemm_out_unnorm_h3_win(c.h, c.M, rows, c.S, Hp, a0, c.ldk, sA, self.W2[L].data_ptr(),
+                                                 c.n_out_pad * 2 * Hp, self.wexp[L].data_ptr(), c.n_out_pad,
+                                                 self.b[L].data_ptr(), c.n_out_pad, preds.data_ptr(), c.S, sP,
+                                                 rexp.data_ptr(), sR, L, s), "amx_gemm_out_unnorm_h3_win")
 
     def _ensure_split_workspace(self, Bp: int) -> None:
         """Register the output layer's split-K scratch with the context when Bp lanes split
@@ -365,6 +417,8 @@ class DeviceEnsemble:
     def _mlp_h3(self, buf, preds, Bp, s, rexp, k_shared=0):
         c = self.ctx
         sA, sR, L = Bp * c.ldk, (c.L + 1) * Bp, c.L
+        if self.plain:
+            return self._mlp_h3_plain(buf, preds, Bp, s, rexp, sA, sR, Bp * c.S, k_shared)
         for i in range(L):
             K = c.k0_pad + i * c.Hp
             N.check(c.lib.amx_gemm_bias_act_h3(c.h, c.M, Bp, c.Hp, K, buf.data_ptr(), c.ldk, sA, self.W2[i].data_ptr(),
@@ -393,25 +447,29 @@ class DeviceEnsemble:
                 e1.record()
                 ev.append((e0, e1, Bp))
             return
+        win = self.layer_windows()  # (first column, K) per layer: the operand by pointer, K and ldk
         for i in range(c.L):
-            K = c.k0_pad + i * c.Hp
+            (c0, K), col = win[i], c.k0_pad + i * c.Hp
+            a0 = buf.data_ptr() + 4 * c0
             if self.W3 is not None:
-                N.check(c.lib.amx_gemm_bias_act_x6(c.h, c.M, Bp, c.Hp, K, buf.data_ptr(), c.ldk, sA,
+                N.check(c.lib.amx_gemm_bias_act_x6(c.h, c.M, Bp, c.Hp, K, a0, c.ldk, sA,
                                                    self.W3[i].data_ptr(), c.Hp * 3 * K, self.b[i].data_ptr(), c.Hp,
-                                                   buf.data_ptr(), c.ldk, sA, K, N.AMX_ACT_RELU, s),
+                                                   buf.data_ptr(), c.ldk, sA, col, N.AMX_ACT_RELU, s),
                         "amx_gemm_bias_act_x6")
             else:
-                N.check(c.lib.amx_gemm_bias_act(c.h, c.M, Bp, c.Hp, K, buf.data_ptr(), c.ldk, sA, self.W[i].data_ptr(),
+                N.check(c.lib.amx_gemm_bias_act(c.h, c.M, Bp, c.Hp, K, a0, c.ldk, sA, self.W[i].data_ptr(),
                                                 K, c.Hp * K, self.b[i].data_ptr(), c.Hp, buf.data_ptr(), c.ldk, sA,
-                                                K, N.AMX_ACT_RELU, s), "amx_gemm_bias_act")
+                                                col, N.AMX_ACT_RELU, s), "amx_gemm_bias_act")
+        c0, K = win[c.L]
+        a0 = buf.data_ptr() + 4 * c0
         if self.W3 is not None:
-            N.check(c.lib.amx_gemm_out_unnorm_x6(c.h, c.M, Bp, c.S, c.ldk, buf.data_ptr(), c.ldk, sA,
-                                                 self.W3[c.L].data_ptr(), c.n_out_pad * 3 * c.ldk,
+            N.check(c.lib.amx_gemm_out_unnorm_x6(c.h, c.M, Bp, c.S, K, a0, c.ldk, sA,
+                                                 self.W3[c.L].data_ptr(), c.n_out_pad * 3 * K,
                                                  self.b[c.L].data_ptr(), c.n_out_pad, preds.data_ptr(), c.S,
                                                  Bp * c.S, s), "amx_gemm_out_unnorm_x6")
         else:
-            N.check(c.lib.amx_gemm_out_unnorm(c.h, c.M, Bp, c.S, c.ldk, buf.data_ptr(), c.ldk, sA,
-                                              self.W[c.L].data_ptr(), c.ldk, c.n_out_pad * c.ldk,
+            N.check(c.lib.amx_gemm_out_unnorm(c.h, c.M, Bp, c.S, K, a0, c.ldk, sA,
+                                              self.W[c.L].data_ptr(), K, c.n_out_pad * K,
                                               self.b[c.L].data_ptr(), c.n_out_pad, preds.data_ptr(), c.S, Bp * c.S, s),
                     "amx_gemm_out_unnorm")
         if ev is not None:
@@ -421,7 +479,10 @@ class DeviceEnsemble:
     def mlp_flops_per_sample(self) -> int:
         """Algorithmic FLOPs of one sample through all members (unpadded shapes)."""
         c, h = self.ctx, self.hidden
-        macs = sum(h * (c.S + c.A + i * h) for i in range(c.L)) + c.S * (c.S + c.A + c.L * h)
+        if self.plain:
+            macs = h * (c.S + c.A) + (c.L - 1) * h * h + c.S * h
+        else:
+            macs = sum(h * (c.S + c.A + i * h) for i in range(c.L)) + c.S * (c.S + c.A + c.L * h)
         return 2 * macs * c.M
 
     def disagreement(self, preds: torch.Tensor, B: int, out: torch.Tensor | None = None) -> torch.Tensor:

@@ -24,9 +24,16 @@ Training (DynamicsEnsemble.train, dynamics.py:82-108, 236-378) runs on the devic
 `train_on_device`, which takes `train`'s arguments and returns what it returns: all members
 advance in lock step, each on the index batches the reference's DataLoaders would have drawn
 for it (`plan_batches`).  `train()` itself keeps raising and names that method (a pinned
-test requires the raise).  The device path implements the dense-connect ReLU BasicMLP
-(dynamics.py:394-433, the README command's `--dynamic_dense_connect`); other model options
-raise NotImplementedError.
+test requires the raise).  `DynamicsEnsemble` implements the dense-connect ReLU BasicMLP
+(dynamics.py:394-433, the README command's `--dynamic_dense_connect`) and
+`PlainDynamicsEnsemble` the plain one (`dense_connect=False`, run.py's default: layer i reads
+layer i-1's output only); `dynamics_ensemble(...)` is the reference's constructor call and returns
+whichever `dense_connect` asks for, so run.py binds it with one import:
+
+    from amp_extensions_amd.ensemble import dynamics_ensemble as DynamicsEnsemble
+
+Other model options (`use_resnet`, a non-ReLU activation, unequal hidden widths) raise
+NotImplementedError.
 
 `as_device_ensemble(obj)` also accepts the reference's own DynamicsEnsemble object (anything
 with `models[k].model.state_dict()`, `transformations` and `threshold`), so SimEnv /
@@ -54,16 +61,24 @@ def basic_mlp_layer_shapes(S: int, A: int, hidden) -> list[tuple[int, int]]:
     return [(sizes[i + 1], sizes[i] + sum(sizes[:i])) for i in range(len(sizes) - 1)]
 
 
+def plain_mlp_layer_shapes(S: int, A: int, hidden) -> list[tuple[int, int]]:
+    """(out, in) of each nn.Linear of a plain BasicMLP (dense_connect=False, dynamics.py:412-420)."""
+    sizes = [S + A] + list(hidden) + [S]
+    return [(sizes[i + 1], sizes[i]) for i in range(len(sizes) - 1)]
+
+
 class BasicMLPWeights(nn.Module):
-    """Host parameter container of one dense-connect BasicMLP (dynamics.py:394-420): the
-    nn.Linear layers in the reference's construction order and state-dict keys.  It has no
+    """Host parameter container of one BasicMLP (dynamics.py:394-420), dense-connect or plain:
+    the nn.Linear layers in the reference's construction order and state-dict keys.  It has no
     forward: the member's arithmetic runs on the GPU (DeviceEnsemble)."""
 
-    def __init__(self, input_dim: int, output_dim: int, hidden_sizes):
+    def __init__(self, input_dim: int, output_dim: int, hidden_sizes, dense_connect: bool = True):
         super().__init__()
         sizes = [input_dim] + list(hidden_sizes) + [output_dim]
+        self.dense_connect = bool(dense_connect)
         self.fc_layers = nn.ModuleList(
-            nn.Linear(sizes[i] + sum(sizes[:i]), sizes[i + 1]) for i in range(len(sizes) - 1))
+            nn.Linear(sizes[i] + (sum(sizes[:i]) if dense_connect else 0), sizes[i + 1])
+            for i in range(len(sizes) - 1))
 
     def layers(self):
         return [(l.weight.data, l.bias.data) for l in self.fc_layers]
@@ -81,17 +96,18 @@ def _make_optimizer(params, optim_args):
     raise AssertionError('Use valid optimizer')
 
 
-def init_model_weights(S: int, A: int, hidden, seed: int):
+def init_model_weights(S: int, A: int, hidden, seed: int, dense_connect: bool = True):
     """DynamicsModel.__init__ RNG order: manual_seed(seed), np.random.seed(seed), then the
     BasicMLP layers constructed in order (dynamics.py:185-196, 419)."""
     torch.manual_seed(seed)
     np.random.seed(seed)
-    return [(w.clone(), b.clone()) for (w, b) in BasicMLPWeights(S + A, S, hidden).layers()]
+    return [(w.clone(), b.clone()) for (w, b) in BasicMLPWeights(S + A, S, hidden, dense_connect).layers()]
 
 
-def init_ensemble_weights(S: int, A: int, hidden, num_models: int = 4, base_seed: int = 100):
+def init_ensemble_weights(S: int, A: int, hidden, num_models: int = 4, base_seed: int = 100,
+                          dense_connect: bool = True):
     """Member k seeded base_seed + k (dynamics.py:70-79)."""
-    return [init_model_weights(S, A, hidden, base_seed + k) for k in range(num_models)]
+    return [init_model_weights(S, A, hidden, base_seed + k, dense_connect) for k in range(num_models)]
 
 
 def weights_from_state_dict(sd) -> list:
@@ -112,7 +128,7 @@ class DynamicsModel:
         # dynamics.py:185-196: the seed, then the layers in construction order
         torch.manual_seed(seed)
         np.random.seed(seed)
-        self.model = BasicMLPWeights(state_dim + action_dim, state_dim, hidden_sizes)
+        self.model = BasicMLPWeights(state_dim + action_dim, state_dim, hidden_sizes, ens.dense_connect)
         self.optimizer = _make_optimizer(self.model.parameters(), optim_args)
 
     def forward(self, state, action, unnormalize_out=True):
@@ -172,12 +188,21 @@ class DynamicsEnsemble:
         device the arithmetic runs on), `ctx` (share an AmxContext), `feat_dim` (the context's
         RFF width), `gemm` (DeviceEnsemble's GEMM path)."""
         if use_resnet or not dense_connect or activation != 'relu':
-            raise NotImplementedError("the device ensemble implements the dense-connect ReLU BasicMLP "
+            raise NotImplementedError("DynamicsEnsemble implements the dense-connect ReLU BasicMLP "
                                       "(dynamics.py:394-433; run.py's --dynamic_dense_connect): got "
-                                      f"use_resnet={use_resnet}, dense_connect={dense_connect}, activation={activation!r}")
+                                      f"use_resnet={use_resnet}, dense_connect={dense_connect}, activation={activation!r}"
+                                      ".  A plain ReLU BasicMLP (dense_connect=False) is PlainDynamicsEnsemble; the "
+                                      "factory dynamics_ensemble(...) returns either by dense_connect")
+        self._setup(state_dim, action_dim, train_dataset, validate_dataset, num_models, batch_size, hidden_sizes,
+                    True, transform, optim_args, device, base_seed, gpu, ctx, feat_dim, gemm)
+
+    def _setup(self, state_dim, action_dim, train_dataset, validate_dataset, num_models, batch_size, hidden_sizes,
+               dense_connect, transform, optim_args, device, base_seed, gpu, ctx, feat_dim, gemm):
+        """The constructor's body, for either connectivity."""
         hidden_sizes = list(hidden_sizes)
-        if len(set(hidden_sizes)) != 1:
+        if len(hidden_sizes) < 1 or len(set(hidden_sizes)) != 1:
             raise NotImplementedError(f"the device ensemble needs equal hidden widths, got {hidden_sizes}")
+        self.dense_connect = bool(dense_connect)
         self.state_dim, self.action_dim = state_dim, action_dim
         self.train_dataset, self.validate_dataset = train_dataset, validate_dataset
         self.batch_size = batch_size
@@ -192,7 +217,11 @@ class DynamicsEnsemble:
                        for k in range(num_models)]
         if ctx is None:
             ctx = AmxContext(state_dim, action_dim, n_models=num_models, hidden=hidden_sizes[0],
-                             n_hidden=len(hidden_sizes), feat_dim=feat_dim, device=_gpu_device(gpu))
+                             n_hidden=len(hidden_sizes), feat_dim=feat_dim, device=_gpu_device(gpu),
+                             dense_connect=self.dense_connect)
+        elif ctx.dense_connect != self.dense_connect:
+            raise ValueError(f"the shared context is {'dense-connect' if ctx.dense_connect else 'plain'}, the "
+                             f"ensemble {'dense-connect' if self.dense_connect else 'plain'}")
         self.ctx = ctx
         self.engine = DeviceEnsemble(ctx, [m.model.layers() for m in self.models], self._norms(), gemm=gemm)
         self._set_member_transformations()
@@ -479,6 +508,43 @@ class DynamicsEnsemble:
         return self.threshold if explicit else None
 
 
+class PlainDynamicsEnsemble(DynamicsEnsemble):
+    """The reference's DynamicsEnsemble with plain members (dense_connect=False, run.py without
+    --dynamic_dense_connect; --dynamic_hidden_sizes defaults to [1024, 1024]): layer i reads
+    layer i-1's output only (dynamics.py:412-433).  Everything else is DynamicsEnsemble's: the
+    members' state dicts and checkpoints in the reference's format, the threshold and
+    discrepancy calls, train_on_device / sync_to_host, from_weights / random_init /
+    from_reference, and the raising train()."""
+
+    def __init__(self, state_dim, action_dim, train_dataset, validate_dataset=None, num_models=4, batch_size=256,
+                 hidden_sizes=[512, 512], use_resnet=False, dense_connect=False, activation='relu', transform=True,
+                 optim_args=DEFAULT_OPTIM_ARGS, device=torch.device('cpu'), base_seed=100, num_workers=1, *,
+                 gpu=None, ctx: AmxContext | None = None, feat_dim: int = 512, gemm: str = "f16x3"):
+        if dense_connect:
+            raise ValueError("PlainDynamicsEnsemble is the dense_connect=False ensemble; dense-connect members are "
+                             "DynamicsEnsemble (or call the factory dynamics_ensemble(...))")
+        if use_resnet or activation != 'relu':
+            raise NotImplementedError("the device ensemble implements the ReLU BasicMLP (dynamics.py:394-433): got "
+                                      f"use_resnet={use_resnet}, activation={activation!r}")
+        self._setup(state_dim, action_dim, train_dataset, validate_dataset, num_models, batch_size, hidden_sizes,
+                    False, transform, optim_args, device, base_seed, gpu, ctx, feat_dim, gemm)
+
+
+def dynamics_ensemble(state_dim, action_dim, train_dataset, validate_dataset=None, num_models=4, batch_size=256,
+                      hidden_sizes=[512, 512], use_resnet=False, dense_connect=False, activation='relu',
+                      transform=True, optim_args=DEFAULT_OPTIM_ARGS, device=torch.device('cpu'), base_seed=100,
+                      num_workers=1, **kw):
+    """The reference's DynamicsEnsemble(...) call (dynamics.py:20-35) with run.py's default for
+    its store_true flag, dense_connect=False: a DynamicsEnsemble when dense_connect, else a
+    PlainDynamicsEnsemble.
+    Keyword extensions (gpu, ctx, feat_dim, gemm) pass through."""
+    cls = DynamicsEnsemble if dense_connect else PlainDynamicsEnsemble
+    return cls(state_dim, action_dim, train_dataset, validate_dataset, num_models=num_models, batch_size=batch_size,
+               hidden_sizes=hidden_sizes, use_resnet=use_resnet, dense_connect=dense_connect, activation=activation,
+               transform=transform, optim_args=optim_args, device=device, base_seed=base_seed,
+               num_workers=num_workers, **kw)
+
+
 def _dataset_tensors(ds):
     """(states, actions, next_states) of an AmpDataset-like dataset (its tensors, or its rows)."""
     if all(hasattr(ds, k) for k in ("states", "actions", "next_states")):
@@ -575,7 +641,9 @@ def as_device_ensemble(ens) -> DeviceEnsemble:
     if conv is None:
         if not (hasattr(ens, "models") and hasattr(ens, "threshold")):
             raise TypeError(f"expected a DynamicsEnsemble, got {type(ens).__name__}")
-        conv = DynamicsEnsemble.from_reference(ens)
+        # the members' own flag (BasicMLP.dense_connect, dynamics.py:409); an object without one is dense
+        dense = bool(getattr(getattr(ens.models[0], "model", None), "dense_connect", True))
+        conv = (DynamicsEnsemble if dense else PlainDynamicsEnsemble).from_reference(ens)
         try:
             ens._amx_ensemble = conv
         except AttributeError:

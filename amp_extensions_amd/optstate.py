@@ -107,6 +107,19 @@ def ensemble_layout(S: int, A: int, hidden: int, L: int, k0_pad: int, Hp: int, l
     return ParamLayout(entries)
 
 
+def plain_ensemble_layout(S: int, A: int, hidden: int, L: int, k0_pad: int, Hp: int, n_out_pad: int) -> ParamLayout:
+    """One member of the plain (dense_connect=False) ensemble (amx_efit_param_count of a plain
+    context): W_0 [Hp][k0_pad], then W_i [Hp][Hp] per further hidden layer and W_out
+    [n_out_pad][Hp], each followed by its bias.  A layer's input columns are those of the one
+    window it reads, so the live block is the leading one."""
+    entries = []
+    for i in range(L + 1):
+        n, k = (n_out_pad if i == L else Hp), (k0_pad if i == 0 else Hp)
+        rows, n_in = (S if i == L else hidden), (S + A if i == 0 else hidden)
+        entries += [((n, k), (rows, n_in)), ((n,), (rows,))]
+    return ParamLayout(entries)
+
+
 # ---- torch.optim state ------------------------------------------------------------------------
 
 def read_state(optimizer, kinds=("adam", "sgd")):

@@ -64,6 +64,16 @@ typedef struct amx_ctx amx_ctx;
  * milo/milo/linear_cost.py:23-62 (feature_dim).  n_hidden hidden layers of width
  * `hidden`, dense-connected (BasicMLP, milo/milo/dynamics.py:394-433). */
 amx_ctx* amx_create(int device, int S, int A, int n_models, int hidden, int n_hidden, int feat_dim);
+/* amx_create with the network's connectivity: AMX_CONNECT_DENSE (amx_create's) or
+ * AMX_CONNECT_PLAIN, BasicMLP(dense_connect=False): hidden layer i >= 1 reads layer i-1's output
+ * only and the output layer the last hidden one (n_hidden >= 1).  The activation rows keep the
+ * dense-concat form [x0 | h0 | h1 | ...] of amx_layout; a plain layer reads the K window
+ * [k0_pad + (i-1) hidden, k0_pad + i hidden) of them against a [hidden][hidden] weight (the
+ * output layer: [n_out_pad][hidden]).  The connectivity sets what amx_efit_param_count,
+ * amx_efit_work_floats, amx_efit_step and amx_split_workspace_floats answer and run. */
+enum { AMX_CONNECT_DENSE = 0, AMX_CONNECT_PLAIN = 1 };
+amx_ctx* amx_create_ex(int device, int S, int A, int n_models, int hidden, int n_hidden, int feat_dim,
+                       int connect);
 int amx_destroy(amx_ctx* ctx);
 const char* amx_last_error(void);
 int amx_abi_version(void);
@@ -208,6 +218,26 @@ int amx_gemm_out_unnorm_h3(amx_ctx* ctx, int groups, int rows, int n_valid, int 
                            long long strideBias, float* preds, int ldp, long long strideP,
                            const int* row_exp, long long strideRexp, int rexp_slots, int k_shared,
                            void* stream);
+
+/* The windowed forms, for a plain (AMX_CONNECT_PLAIN) chain: A points at the K window the layer
+ * reads (row stride lda still the whole activation row) and the rows are scaled by the one
+ * exponent slot `rexp_first` of that window, not by a max over leading slots (row_exp is the
+ * base of the [groups][slots][rows] table, strideRexp >= (rexp_first + 1) rows).  `first_layer`
+ * (0 / 1) marks the launch at which amx_set_gemm_timer's forward starts; the two-argument
+ * forms infer it from rexp_slots == 1, which in a plain chain holds for every layer.  Same
+ * tiles, epilogues and split workspace as the forms above (no k_shared: a window past x0 is
+ * every group's own). */
+int amx_gemm_bias_act_h3_win(amx_ctx* ctx, int groups, int rows, int N, int K, const float* A, int lda,
+                             long long strideA, const uint16_t* W2, long long strideW2, const int* w_exp,
+                             long long strideWexp, const float* bias, long long strideBias, float* C,
+                             int ldc, long long strideC, int col_off, int act, const int* row_exp,
+                             long long strideRexp, int rexp_first, int* row_exp_out, int first_layer,
+                             void* stream);
+int amx_gemm_out_unnorm_h3_win(amx_ctx* ctx, int groups, int rows, int n_valid, int K, const float* A,
+                               int lda, long long strideA, const uint16_t* W2, long long strideW2,
+                               const int* w_exp, long long strideWexp, const float* bias,
+                               long long strideBias, float* preds, int ldp, long long strideP,
+                               const int* row_exp, long long strideRexp, int rexp_first, void* stream);
 
 /* f16x3 form of amx_rff_features (RBFLinearCost.get_rep, milo/milo/linear_cost.py:64-71):
  * W2/w_exp = amx_split_f16x2 image of the [F][K] RFF weight, row_exp [rows] = exponents of x's
@@ -569,8 +599,9 @@ int amx_counter_add(amx_ctx* ctx, uint64_t* counter, long long delta, void* stre
 /* GEMM timing that works inside captured HIP graphs (ROCm has no timing-event nodes) and adds
  * no launches: with buf set (4 uint64 of device memory, zeroed by the caller), every f16x3
  * ensemble forward on this context records the device's 100 MHz realtime counter when its
- * first hidden layer starts (amx_gemm_bias_act_h3 with rexp_slots = 1: block 0, buf[0]) and,
- * when the last workgroup of its output layer (amx_gemm_out_unnorm_h3) finishes, adds the
+ * first hidden layer starts (amx_gemm_bias_act_h3 with rexp_slots = 1, or the windowed form
+ * with first_layer = 1: block 0, buf[0]) and, when the last workgroup of its output layer
+ * (amx_gemm_out_unnorm_h3 or its windowed form) finishes, adds the
  * elapsed ticks to buf[2] and 1 to buf[3] (buf[1]: arrival counter, left zero).  The pointer
  * is read when a launch is issued (graph capture bakes it in).  null: off. */
 int amx_set_gemm_timer(amx_ctx* ctx, uint64_t* buf);
@@ -584,7 +615,8 @@ int amx_set_gemm_timer(amx_ctx* ctx, uint64_t* buf);
  * of the shapes above) and *n_counters uint32 counters a forward of `rows` padded lanes needs, 0 when that shape
  * does not use it.  amx_set_split_workspace registers caller-owned device memory with the
  * context (counters zeroed by the caller once; each launch leaves them zero); without it the
- * layer runs on row-block tiles.  One launch at a time per context. */
+ * layer runs on row-block tiles.  One launch at a time per context.  The sizes follow the
+ * context's connectivity (a plain layer's K is `hidden`). */
 long long amx_split_workspace_floats(const amx_ctx* ctx, int groups, int rows, int* n_counters);
 
 int amx_set_split_workspace(amx_ctx* ctx, float* scratch, long long floats, uint32_t* counters,
@@ -790,7 +822,8 @@ enum { AMX_EFIT_ADAM = 0, AMX_EFIT_SGD = 1 };
  * amx_last_error for an unsupported depth).  amx_efit_param_count: floats per member of the
  * flat gradient and of each optimizer-state vector, laid out layer by layer as
  * W_i [N_i][K_i] | b_i [N_i] in the engine's padded dense-concat layout (N_i = hidden, K_i =
- * k0_pad + i*hidden; the last layer N = n_out_pad, K = ldk).  amx_efit_work_floats: floats of
+ * k0_pad + i*hidden; the last layer N = n_out_pad, K = ldk; on an AMX_CONNECT_PLAIN context
+ * K_0 = k0_pad and K_i = hidden for every later layer).  amx_efit_work_floats: floats of
  * the opaque step workspace for batches padded to Bt rows (Bt % 128 == 0). */
 long long amx_efit_param_count(const amx_ctx* ctx);
 long long amx_efit_work_floats(const amx_ctx* ctx, int Bt);

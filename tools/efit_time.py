@@ -8,8 +8,11 @@ The device epochs are timed with events around whole epochs (index upload, every
 launches, the loss read-back), after a warm-up epoch; both sides start from the same weights
 and take the same index batches, and their epoch losses are printed side by side.
 
-usage: python tools/efit_time.py [out.txt] [cpu_threads] [--no-host]
-(--no-host: the device part only, for a kernel-trace run of its own)
+usage: python tools/efit_time.py [out.txt] [cpu_threads] [--no-host] [--plain] [--forward]
+(--no-host: the device part only, for a kernel-trace run of its own; --plain: run.py's default
+model instead -- plain members, dense_connect=False, hidden [1024, 1024] -- through
+PlainDynamicsEnsemble and tests/plain_ref.py, plus the f16x3 inference forward of 256 lanes timed
+in-kernel, AmxContext.gemm_timer; --forward: that forward line for the dense-connect shape too)
 """
 import copy
 import os
@@ -23,14 +26,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from amp_extensions_amd.datasets import AmpDataset  # noqa: E402
-from amp_extensions_amd.ensemble import DynamicsEnsemble, index_loader, materialise, plan_batches  # noqa: E402
+from amp_extensions_amd.ensemble import (DynamicsEnsemble, PlainDynamicsEnsemble, index_loader, materialise,  # noqa: E402
+                                         plan_batches)
 from efit_ref import events_from_plan, restate_member, synthetic_transitions  # noqa: E402
+from plain_ref import restate_member as restate_plain_member  # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 no_host = "--no-host" in sys.argv
-out_path = args[0] if args else os.path.join("profiles", "efit_time.txt")
+plain = "--plain" in sys.argv
+out_path = args[0] if args else os.path.join("profiles", "efit_time_plain.txt" if plain else "efit_time.txt")
 threads = int(args[1]) if len(args) > 1 else 16
 S, A, HIDDEN, M, BATCH, N, EPOCHS, CLIP = 197, 36, [512] * 4, 4, 256, 20480, 2, 1.0
+if plain:
+    HIDDEN, DynamicsEnsemble, restate_member = [1024, 1024], PlainDynamicsEnsemble, restate_plain_member
 OPT = {"optim": "adam", "lr": 1e-3, "eps": 1e-8}
 steps = -(-N // BATCH)
 
@@ -71,13 +79,35 @@ for e in range(1, EPOCHS + 1):
     dev_loss.append([float(np.average([float(x) for x in losses[g]])) for g in range(M)])
 eng.fit_end()
 dev_total = sum(dev_ms)
+
+
+def forward_us(e, reps=200):
+    """Mean in-kernel time of the f16x3 forward of BATCH lanes (first hidden layer's start to the
+    output layer's last workgroup, AmxContext.gemm_timer), after a warm-up."""
+    ob, ac = tr[0][:BATCH].cuda(), tr[1][:BATCH].cuda()
+    for _ in range(10):
+        e.forward_preds(ob, ac, BATCH)
+    timer = e.ctx.gemm_timer()
+    for _ in range(reps):
+        e.forward_preds(ob, ac, BATCH)
+    torch.cuda.synchronize()
+    t = timer.cpu().tolist()
+    e.ctx.gemm_timer(False)
+    assert t[3] == reps, t
+    return t[2] / t[3] / 100.0  # 100 MHz ticks
+
+
 lines = [
-    f"ensemble training, {M} members, hidden {HIDDEN}, S/A {S}/{A}, batch {BATCH}, {N} rows: {EPOCHS} epochs x "
+    f"ensemble training, {M} {'plain' if plain else 'dense-connect'} members, hidden {HIDDEN}, S/A {S}/{A}, "
+    f"batch {BATCH}, {N} rows: {EPOCHS} epochs x "
     f"{steps} steps of Adam, grad_clip {CLIP}",
     f"device ({torch.cuda.get_device_name(0)}): fit_epoch, events around whole epochs after a warm-up epoch: "
     + ", ".join(f"{x:.1f}" for x in dev_ms) + f" ms; {dev_total / (EPOCHS * steps) * 1e3:.1f} us per step "
     f"(all {M} members)",
 ]
+if plain or "--forward" in sys.argv:
+    lines.append(f"f16x3 inference forward, {BATCH} lanes x {M} members, in-kernel (gemm_timer, mean of 200): "
+                 f"{forward_us(eng):.1f} us")
 if not no_host:
     torch.set_num_threads(threads)
     data = {"train": tr}
