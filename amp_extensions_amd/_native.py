@@ -111,6 +111,10 @@ SIGNATURES = {
     "amx_npg_ll": (c_int, [vp, c_int, vp, c_ll, vp, c_ll, vp, vp, vp, vp, vp]),
     "amx_npg_apply_step": (c_int, [vp, c_int, c_int, vp, vp, vp, c_int, c_dbl, c_dbl, c_flt, vp, vp, vp]),
     "amx_npg_pass_ex": (c_int, [vp, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, vp, c_int, vp, vp, vp, vp]),
+    "amx_npg_pass_dp": (c_int, [vp, c_int, c_int, vp, c_int, c_ll, vp, c_int, c_ll, vp, vp, vp, c_int, vp, vp, vp, c_ll,
+                                vp]),
+    "amx_npg_pass_cg_dp": (c_int, [vp, c_int, vp, c_int, c_ll, vp, c_int, vp, vp, c_dbl, vp, vp, vp, vp, vp, vp, vp,
+                                   vp, vp, c_ll, vp]),
     "amx_npg_cg_init": (c_int, [vp, c_int, vp, vp, vp, vp, vp, vp, vp]),
     "amx_npg_cg_init_ls": (c_int, [vp, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "amx_npg_cg_step": (c_int, [vp, c_int, c_int, vp, vp, c_dbl, c_dbl, vp, vp, vp, vp, vp, vp]),
@@ -155,6 +159,8 @@ SIGNATURES = {
     "amx_value_head": (c_int, [vp, c_int, vp, c_int, c_int, vp, vp, vp, vp]),
     "amx_gae": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, vp, vp, c_ll, vp, c_dbl, c_dbl, vp, vp, vp]),
     "amx_adv_whiten": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, c_dbl, vp, vp, vp]),
+    "amx_adv_whiten_parts": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, c_int, c_int, vp, vp]),
+    "amx_adv_whiten_apply": (c_int, [vp, c_int, c_int, vp, vp, c_ll, vp, vp, c_int, c_dbl, vp, vp, vp]),
     "amx_vfit_work": (c_ll, [c_int, c_int, c_int]),
     "amx_vfit_param_count": (c_ll, [c_int, c_int, c_int]),
     "amx_vfit_epoch": (c_int, [vp, c_int, vp, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,

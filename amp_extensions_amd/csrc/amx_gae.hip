@@ -201,12 +201,11 @@ __global__ __launch_bounds__(1024) void k_whiten_part(Grid g, const double* __re
   }
 }
 
-__global__ __launch_bounds__(1024) void k_whiten_apply(Grid g, const double* __restrict__ adv,
-                                                       const double* __restrict__ part, int nb, long long ch,
-                                                       double eps, double* __restrict__ out,
-                                                       double* __restrict__ stats) {
-  const long long total = (long long)g.T * g.L;
-  const bool flat = g.T == 1 && g.len == nullptr && g.base == nullptr;
+// the combine of nb parts in order (every thread the same bits): count, mean, M2 about that mean
+struct WhitenStats {
+  double n, mean, m2;
+};
+__device__ inline WhitenStats whiten_combine(const double* __restrict__ part, int nb) {
   double n = 0.0, dev = 0.0, a = 0.0;
   bool have = false;
   for (int b = 0; b < nb; ++b) {  // every thread the same fixed order (broadcast loads)
@@ -224,6 +223,19 @@ __global__ __launch_bounds__(1024) void k_whiten_apply(Grid g, const double* __r
     const double nbk = part[4 * b], d = part[4 * b + 1] - mean;
     m2 += part[4 * b + 2] + (2.0 * d * part[4 * b + 3] + nbk * d * d);
   }
+  return WhitenStats{n, mean, m2};
+}
+
+// part: amx_adv_whiten's nb per-block parts, or (amx_adv_whiten_apply) the ranks' records; the
+// grid and ch are always those of the local rows
+__global__ __launch_bounds__(1024) void k_whiten_apply(Grid g, const double* __restrict__ adv,
+                                                       const double* __restrict__ part, int nb, long long ch,
+                                                       double eps, double* __restrict__ out,
+                                                       double* __restrict__ stats) {
+  const long long total = (long long)g.T * g.L;
+  const bool flat = g.T == 1 && g.len == nullptr && g.base == nullptr;
+  const WhitenStats w = whiten_combine(part, nb);
+  const double n = w.n, mean = w.mean, m2 = w.m2;
   const double sd = n > 0.0 ? sqrt(m2 / n) : 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 0 && stats) {
     stats[0] = mean;
@@ -235,6 +247,35 @@ __global__ __launch_bounds__(1024) void k_whiten_apply(Grid g, const double* __r
     long long r = 0;
     if (whiten_elem(g, flat, i, c1, r)) out[r] = (adv[r] - mean) / den;
   }
+}
+
+// amx_adv_whiten_parts: the block parts -> the rank's record (n, mean, M2, R) in rec, combined as
+// k_whiten_apply combines them.  R = sum_b R_b + n_b (m_b - mean) is what the mean's rounding left
+// of the rank's sum; a single record then gives mean + R / n as the mean again, so R is halved
+// until that is `mean` itself (never, unless the mean's two roundings left it more than half an
+// ulp off): one record reproduces amx_adv_whiten's stats bit for bit (d = 0: M2 + 0).
+__global__ __launch_bounds__(64) void k_whiten_record(const double* __restrict__ part, int nb,
+                                                      double* __restrict__ rec) {
+  if (threadIdx.x != 0) return;
+  const WhitenStats w = whiten_combine(part, nb);
+  double res = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    const double nbk = part[4 * b];
+    if (nbk > 0.0) res += part[4 * b + 3] + nbk * (part[4 * b + 1] - w.mean);
+  }
+  for (int k = 0; k < 64 && w.n > 0.0 && w.mean + res / w.n != w.mean; ++k) res *= 0.5;
+  rec[0] = w.n;
+  rec[1] = w.mean;
+  rec[2] = w.m2;
+  rec[3] = res;
+}
+
+// the first pass's partition of `total` elements: chunk per workgroup (WCH, or larger multiples of
+// 1024 beyond AMX_WHITEN_MAXB workgroups) and the workgroup count
+inline long long whiten_chunks(long long total, long long& ch) {
+  ch = WCH;
+  if ((total + ch - 1) / ch > AMX_WHITEN_MAXB) ch = ((total + AMX_WHITEN_MAXB - 1) / AMX_WHITEN_MAXB + 1023) / 1024 * 1024;
+  return total > 0 ? (total + ch - 1) / ch : 1;
 }
 
 int check_grid(const char* fn, int T, int L, long long stride) {
@@ -295,16 +336,53 @@ extern "C" int amx_adv_whiten(amx_ctx* ctx, int T, int L, const int32_t* len, co
   int rc = check_grid("amx_adv_whiten", T, L, stride);
   if (rc) return rc;
   AMX_CHECK_ARG(adv && out, "amx_adv_whiten: null pointer");
-  const long long total = (long long)T * L;
-  long long ch = WCH;  // chunk per workgroup: WCH, or larger (multiples of 1024) beyond MAXB workgroups
-  if ((total + ch - 1) / ch > AMX_WHITEN_MAXB) ch = ((total + AMX_WHITEN_MAXB - 1) / AMX_WHITEN_MAXB + 1023) / 1024 * 1024;
-  const long long nb = total > 0 ? (total + ch - 1) / ch : 1;
+  long long ch;
+  const long long nb = whiten_chunks((long long)T * L, ch);
   Grid g{T, L, len, base, stride};
   hipLaunchKernelGGL(k_whiten_part, dim3((int)nb), dim3(1024), 0, (hipStream_t)stream, g, adv, ch,
                      ctx->d_whiten_part);
   AMX_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_whiten_apply, dim3((int)nb), dim3(1024), 0, (hipStream_t)stream, g, adv, ctx->d_whiten_part,
                      (int)nb, ch, eps, out, stats);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+extern "C" int amx_adv_whiten_parts(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base,
+                                    long long stride, const double* adv, int rank, int world, double* msg,
+                                    void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_adv_whiten_parts: null ctx");
+  int rc = check_grid("amx_adv_whiten_parts", T, L, stride);
+  if (rc) return rc;
+  AMX_CHECK_ARG(adv && msg, "amx_adv_whiten_parts: null pointer");
+  AMX_CHECK_ARG(world >= 1 && world <= AMX_WHITEN_MAXB && rank >= 0 && rank < world,
+                "amx_adv_whiten_parts: rank=%d world=%d (<= %d)", rank, world, AMX_WHITEN_MAXB);
+  long long ch;
+  const long long nb = whiten_chunks((long long)T * L, ch);
+  Grid g{T, L, len, base, stride};
+  hipLaunchKernelGGL(k_whiten_part, dim3((int)nb), dim3(1024), 0, (hipStream_t)stream, g, adv, ch,
+                     ctx->d_whiten_part);
+  AMX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_whiten_record, dim3(1), dim3(64), 0, (hipStream_t)stream, ctx->d_whiten_part, (int)nb,
+                     msg + 4 * (long long)rank);
+  AMX_CHECK_LAUNCH();
+  return AMX_OK;
+}
+
+extern "C" int amx_adv_whiten_apply(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base,
+                                    long long stride, const double* adv, const double* msg, int world, double eps,
+                                    double* out, double* stats, void* stream) {
+  AMX_CHECK_ARG(ctx, "amx_adv_whiten_apply: null ctx");
+  int rc = check_grid("amx_adv_whiten_apply", T, L, stride);
+  if (rc) return rc;
+  AMX_CHECK_ARG(adv && msg && out, "amx_adv_whiten_apply: null pointer");
+  AMX_CHECK_ARG(world >= 1 && world <= AMX_WHITEN_MAXB, "amx_adv_whiten_apply: world=%d (<= %d)", world,
+                AMX_WHITEN_MAXB);
+  long long ch;
+  const long long nb = whiten_chunks((long long)T * L, ch);
+  Grid g{T, L, len, base, stride};
+  hipLaunchKernelGGL(k_whiten_apply, dim3((int)nb), dim3(1024), 0, (hipStream_t)stream, g, adv, msg, world, ch, eps,
+                     out, stats);
   AMX_CHECK_LAUNCH();
   return AMX_OK;
 }

@@ -104,6 +104,9 @@ typedef float pf4 __attribute__((ext_vector_type(4)));
 struct NpgArgs {
   int mode, N, S, A;
   int rows_per_block;
+  // the divisor of the means (amx_npg_pass_dp: the row count over every rank of a data-parallel
+  // update; every other entry point: N).  Rows, blocks and the hcache stay this pass's own N.
+  long long n_total;
   const void* obs; long long ldo;
   // FVP reads neither actions nor advantages: the IDX kernels (amx_npg_pass_idx /
   // amx_npg_pass_cg_idx) take their two operands in those slots, so the argument block keeps its
@@ -514,7 +517,7 @@ __global__ __launch_bounds__(NT, 1) void k_npg(NpgArgs a) {
 #pragma unroll
   for (int s = 0; s < G3SLOTS; ++s) g3[s] = pf4{0.f, 0.f, 0.f, 0.f};
   double gls = 0.0, ev_surr = 0.0, ev_kl = 0.0;
-  const double invN = 1.0 / (double)a.N;
+  const double invN = 1.0 / (double)a.n_total;
 
   for (int c0 = r0, ci = 0; c0 < r1; c0 += RC, ++ci) {
     // per-chunk opaque copies of the lane indices and strides: keeps the compiler from hoisting
@@ -1294,11 +1297,12 @@ namespace {
 int npg_launch(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, long long ldo, const void* act,
                int act_dtype, long long lda, const double* adv, const float* theta, const float* vec,
                int rows_per_block, double* partials, const double* gate, float* hcache, const NpgArgs* cg,
-               void* stream, const int* row_idx = nullptr, double* prod_count = nullptr) {
+               void* stream, const int* row_idx = nullptr, double* prod_count = nullptr, long long n_total = 0) {
   const int S = ctx->S, A = ctx->A;
   NpgArgs a = {};
   if (cg) a = *cg;
   a.mode = mode; a.N = N; a.S = S; a.A = A; a.rows_per_block = rows_per_block;
+  a.n_total = n_total > 0 ? n_total : N;  // 0: the pass's own rows (every entry point but the _dp ones)
   a.obs = obs; a.ldo = ldo;
   a.act = act; a.lda = lda;
   a.adv = adv; a.theta = theta; a.vec = vec; a.partials = partials; a.gate = gate; a.hcache = hcache;
@@ -1354,6 +1358,14 @@ extern "C" int amx_npg_pass_ex(amx_ctx* ctx, int mode, int N, const void* obs, i
                                const void* act, int act_dtype, long long lda, const double* adv, const float* theta,
                                const float* vec, int rows_per_block, double* partials, const double* gate,
                                float* hcache, void* stream) {
+  return amx_npg_pass_dp(ctx, mode, N, obs, obs_dtype, ldo, act, act_dtype, lda, adv, theta, vec, rows_per_block,
+                         partials, gate, hcache, N, stream);
+}
+
+extern "C" int amx_npg_pass_dp(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, long long ldo,
+                               const void* act, int act_dtype, long long lda, const double* adv, const float* theta,
+                               const float* vec, int rows_per_block, double* partials, const double* gate,
+                               float* hcache, long long n_total, void* stream) {
   AMX_CHECK_ARG(ctx, "amx_npg_pass: null ctx");
   const int S = ctx->S, A = ctx->A;
   AMX_CHECK_ARG(mode >= NPG_VPG && mode <= NPG_EVAL, "amx_npg_pass: mode=%d", mode);
@@ -1367,8 +1379,10 @@ extern "C" int amx_npg_pass_ex(amx_ctx* ctx, int mode, int N, const void* obs, i
   AMX_CHECK_ARG(ldo >= S && lda >= A, "amx_npg_pass: ldo=%lld lda=%lld", ldo, lda);
   AMX_CHECK_ARG(((uintptr_t)theta & 15) == 0 && ((uintptr_t)vec & 15) == 0,
                 "amx_npg_pass: theta / vec must be 16-byte aligned (W1 is read as float4s)");
+  // (after the N > 0 check above: n_total == N, the plain entry points, never fails here)
+  AMX_CHECK_ARG(n_total >= N && n_total >= 1, "amx_npg_pass_dp: n_total=%lld (>= N=%d, >= 1)", n_total, N);
   return npg_launch(ctx, mode, N, obs, obs_dtype, ldo, act, act_dtype, lda, adv, theta, vec, rows_per_block, partials,
-                    gate, hcache, nullptr, stream);
+                    gate, hcache, nullptr, stream, nullptr, nullptr, n_total);
 }
 
 namespace {
@@ -1398,6 +1412,15 @@ extern "C" int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dty
                                double* x, const double* r_in, double* r_out, const double* p_in, double* p_out,
                                float* p32_out, const double* state_in, double* state_out, const double* work,
                                void* stream) {
+  return amx_npg_pass_cg_dp(ctx, N, obs, obs_dtype, ldo, theta, rows_per_block, partials, hcache, tol, x, r_in, r_out,
+                            p_in, p_out, p32_out, state_in, state_out, work, N, stream);
+}
+
+extern "C" int amx_npg_pass_cg_dp(amx_ctx* ctx, int N, const void* obs, int obs_dtype, long long ldo,
+                                  const float* theta, int rows_per_block, double* partials, float* hcache, double tol,
+                                  double* x, const double* r_in, double* r_out, const double* p_in, double* p_out,
+                                  float* p32_out, const double* state_in, double* state_out, const double* work,
+                                  long long n_total, void* stream) {
   AMX_CHECK_ARG(ctx, "amx_npg_pass_cg: null ctx");
   const int S = ctx->S, A = ctx->A;
   AMX_CHECK_ARG(S > 0 && S <= MAXS && A > 0 && A <= MAXA, "amx_npg_pass_cg: S=%d (<= %d), A=%d (<= %d)", S, MAXS,
@@ -1410,8 +1433,9 @@ extern "C" int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dty
   int rc = npg_fold_args("amx_npg_pass_cg", ctx, tol, x, r_in, r_out, p_in, p_out, p32_out, state_in, state_out, work,
                          &cg);
   if (rc) return rc;
+  AMX_CHECK_ARG(n_total >= N && n_total >= 1, "amx_npg_pass_cg_dp: n_total=%lld (>= N=%d, >= 1)", n_total, N);
   return npg_launch(ctx, NPG_FVP, N, obs, obs_dtype, ldo, obs, AMX_IN_F32, A, nullptr, theta, nullptr,
-                    rows_per_block, partials, nullptr, hcache, &cg, stream);
+                    rows_per_block, partials, nullptr, hcache, &cg, stream, nullptr, nullptr, n_total);
 }
 
 namespace {

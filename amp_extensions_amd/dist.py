@@ -20,6 +20,13 @@ def world() -> tuple[int, int, int]:
         int(os.environ.get("LOCAL_RANK", "0"))
 
 
+def rank_world() -> tuple[int, int]:
+    """(rank, world_size) of the initialised process group, (0, 1) without one."""
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
 def allreduce_sum(t: torch.Tensor) -> torch.Tensor:
     """In-place SUM over ranks (no-op without an initialised process group)."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:

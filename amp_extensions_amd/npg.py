@@ -16,6 +16,11 @@ reference draws them; the BC term of NPG.CPI_surrogate (npg_cg.py:79-84) is one 
 the expert rows with every advantage equal to reg_coeff, and a log-likelihood pass (amx_npg_ll) for
 the surrogate's values.
 
+With the rollout sharded over ranks the update runs data-parallel (`allreduce=`):
+each rank passes its own rows, the passes divide by the global row count (amx_npg_pass_dp), and the
+whitening records, the gradient, every CG iteration's Fisher-vector product and the evaluation sums
+cross the ranks as one small fp64 all-reduce each.
+
 `NPG` is the drop-in (the reference's constructor, `train_from_paths(paths, infos)`, `logger`,
 `running_score`), built like ppo.PPO: `class NPG(amx.NPG, BatchREINFORCE): pass`.
 """
@@ -127,10 +132,12 @@ class DeviceNPG:
         # one block per CU (the pass kernel holds ~140 KB of LDS): one wave of blocks
         return max(32, int(math.ceil(n / 256 / 32)) * 32)
 
-    def _pass(self, mode, obs, act, adv, vec, gate=None, hcache=None, reduce=True, out=None, part=None):
+    def _pass(self, mode, obs, act, adv, vec, gate=None, hcache=None, reduce=True, out=None, part=None,
+              n_total=None):
         """One pass (amx_npg_pass_ex) and its block-order reduction (into `out` when given);
         reduce=False returns the [blocks][width] partials instead (the CG folds their reduction
-        into its step).  `part`: the rows of a larger partials buffer to write (no reduction)."""
+        into its step).  `part`: the rows of a larger partials buffer to write (no reduction).
+        `n_total`: the divisor of a data-parallel update (amx_npg_pass_dp: the rows of every rank)."""
         c = self.ctx
         n = obs.shape[0]
         rpb = self._rows_per_block(n)
@@ -147,11 +154,18 @@ class DeviceNPG:
         od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
         ad = N.AMX_IN_F64 if act.dtype == torch.float64 else N.AMX_IN_F32
         g = None if gate is None else gate.data_ptr()
-        N.check(c.lib.amx_npg_pass_ex(c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad,
-                                      act.stride(0), None if adv is None else adv.data_ptr(),
-                                      self.theta.data_ptr(), None if vec is None else vec.data_ptr(), rpb,
-                                      part.data_ptr(), g, None if hcache is None else hcache.data_ptr(), c.stream),
-                "amx_npg_pass")
+        if n_total is None:
+            N.check(c.lib.amx_npg_pass_ex(c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad,
+                                          act.stride(0), None if adv is None else adv.data_ptr(),
+                                          self.theta.data_ptr(), None if vec is None else vec.data_ptr(), rpb,
+                                          part.data_ptr(), g, None if hcache is None else hcache.data_ptr(),
+                                          c.stream), "amx_npg_pass")
+        else:
+            N.check(c.lib.amx_npg_pass_dp(c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad,
+                                          act.stride(0), None if adv is None else adv.data_ptr(),
+                                          self.theta.data_ptr(), None if vec is None else vec.data_ptr(), rpb,
+                                          part.data_ptr(), g, None if hcache is None else hcache.data_ptr(),
+                                          int(n_total), c.stream), "amx_npg_pass_dp")
         if not reduce:
             return part
         if out is None:
@@ -398,7 +412,7 @@ class DeviceNPG:
         return np.asarray(rows, dtype=np.int32).reshape(self.cg_iters, m), states
 
     def train_from_arrays(self, observations, actions, advantages, whiten: bool = True, bc=None,
-                          dist_info=None, idx=None) -> dict:
+                          dist_info=None, idx=None, *, allreduce=None, rank: int = 0, world: int = 1) -> dict:
         """NPG.train_from_paths on concatenated arrays (npg_cg.py:113-199): whitening
         (batch_reinforce.py:284-285), VPG, CG, step size, update with the log_std clamp,
         surr_after and kl_dist.  Returns the reference's infos entries.
@@ -409,10 +423,18 @@ class DeviceNPG:
         the old, where the reference's last CPI_surrogate call takes them.  `idx`: the
         [cg_iters][M] rows of the subsampled Fisher; by default, with hvp_sample_frac < 0.99, they
         are drawn as the reference draws them and numpy's generator is left after as many draws
-        as the solve took products.  With none of these the update is the plain one."""
+        as the solve took products.  With none of these the update is the plain one.
+
+        `allreduce` (with `rank`, `world`; taken from torch.distributed's group when one is
+        initialised): the rows are this rank's share of a data-parallel update over `world` ranks
+        (see _train_dp); `allreduce(t)` sums a device tensor in place over the ranks, as
+        RolloutEngine.relabel's.  None: the single-process update, unchanged."""
         bc = self.bc if bc is None else bc
         dist_info = self.dist_info if dist_info is None else dist_info
         sub = idx is not None or (self.hvp_subsample is not None and self.hvp_subsample < 0.99)
+        if allreduce is not None:
+            return self._train_dp(observations, actions, advantages, whiten, bc, dist_info, sub, allreduce, rank,
+                                  world)
         if bc is not None or dist_info or sub or self.eval_before:
             return self._train_ext(observations, actions, advantages, whiten, bc, dist_info, idx, sub)
         obs, act, adv = self._inputs(observations, actions, advantages)
@@ -507,25 +529,151 @@ class DeviceNPG:
                     "kl_dist": kl_h / n, "advantages": adv, "hvp_products": self.hvp_products})
         return out
 
-    def train_from_paths(self, paths, infos: dict | None = None):
+    # ---- the data-parallel update ----------------------------------------------------------
+    def _cg_solve_dp(self, obs, act, b: torch.Tensor, hcache, n_total: int, allreduce) -> torch.Tensor:
+        """cg_solve's folded form for one rank of a data-parallel update.  Per iteration: the
+        Fisher-vector pass over the rank's rows divided by n_total (amx_npg_pass_dp on p32, then
+        amx_npg_pass_cg_dp with the previous vector step folded in), the rank's column sums as one
+        [P] message (amx_npg_reduce_gated), `allreduce`, and amx_npg_cg_reduce on the summed message
+        as a one-block partials buffer: z, p.z and the vector step are formed from the same bits on
+        every rank.  The host cannot see the early stop, so it always runs cg_iters collectives; a
+        stopped solve (the same stop on every rank) leaves the message alone: the collective then
+        re-sums finite values nobody reads."""
+        c, P, dev = self.ctx, self.P, self.ctx.device
+        b = b.to(torch.float64).contiguous()
+        x, r, p, r2, p2 = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(5))
+        p32, p32b = (torch.empty(P, dtype=torch.float32, device=dev) for _ in range(2))
+        state, state2 = (torch.empty(2, dtype=torch.float64, device=dev) for _ in range(2))
+        curv = torch.empty(self.A, dtype=torch.float64, device=dev)
+        msg = torch.zeros(P, dtype=torch.float64, device=dev)
+        N.check(c.lib.amx_npg_cg_init_ls(c.h, P, self.A, self.theta.data_ptr(), curv.data_ptr(), b.data_ptr(),
+                                         x.data_ptr(), r.data_ptr(), p.data_ptr(), p32.data_ptr(), state.data_ptr(),
+                                         c.stream), "amx_npg_cg_init_ls")
+        work = self._bufs.get("cg_work")
+        if work is None:
+            work = self._bufs["cg_work"] = torch.empty(int(c.lib.amx_npg_cg_tail_work(P)), dtype=torch.float64,
+                                                       device=dev)
+        hc = hcache if obs.dtype == torch.float32 else None
+        n = obs.shape[0]
+        rpb = self._rows_per_block(n)
+        od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
+        for it in range(self.cg_iters):
+            if it == 0:
+                part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False, n_total=n_total)
+            else:
+                N.check(c.lib.amx_npg_pass_cg_dp(c.h, n, obs.data_ptr(), od, obs.stride(0), self.theta.data_ptr(), rpb,
+                                                 part.data_ptr(), N.ptr(hc), self.residual_tol, x.data_ptr(),
+                                                 r.data_ptr(), r2.data_ptr(), p.data_ptr(), p2.data_ptr(),
+                                                 p32b.data_ptr(), state.data_ptr(), state2.data_ptr(),
+                                                 work.data_ptr(), int(n_total), c.stream), "amx_npg_pass_cg_dp")
+                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
+            N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), part.shape[0], P, msg.data_ptr(),
+                                               state.data_ptr(), c.stream), "amx_npg_reduce")
+            allreduce(msg)
+            N.check(c.lib.amx_npg_cg_reduce(c.h, msg.data_ptr(), 1, P, self.A, curv.data_ptr(), self.damping,
+                                            p.data_ptr(), p32.data_ptr(), state.data_ptr(), work.data_ptr(),
+                                            c.stream), "amx_npg_cg_reduce")
+        if self.cg_iters > 0:
+            N.check(c.lib.amx_npg_cg_xrp(c.h, P, self.residual_tol, x.data_ptr(), r.data_ptr(), r2.data_ptr(),
+                                         p.data_ptr(), p32.data_ptr(), state.data_ptr(), state2.data_ptr(),
+                                         work.data_ptr(), c.stream), "amx_npg_cg_xrp")
+        return x
+
+    def _train_dp(self, observations, actions, advantages, whiten, bc, dist_info, sub, allreduce, rank, world):
+        """train_from_arrays for one rank of a data-parallel update: the rows are this rank's
+        share, the update is the union's.  The collectives of one update, in this order on every
+        rank (each `allreduce(t)` on the context's stream order):
+          1. the row counts, int64 [world] (slot `rank` = the local n; the one extra host sync);
+          2. the whitening records, fp64 [world][4] (only with `whiten`);
+          3. the VPG, fp64 [P];
+          4. cg_iters messages, fp64 [P] (see _cg_solve_dp);
+          5. the EVAL sums, fp64 [2].
+        Every pass divides by the global count; vpg_grad, npg_grad, alpha, delta, the new theta,
+        surr_after and kl_dist are global and, given a collective that leaves the same bits on
+        every rank, identical on all of them; `advantages` are the rank's own rows whitened with
+        the global statistics.  A rank without rows makes every rank raise the same ValueError
+        after the count exchange; a BC term, a subsampled Fisher, dist_info or eval_before raise
+        NotImplementedError before any collective (numpy's draw order has no multi-rank meaning)."""
+        from . import dist as D
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = D.rank_world()
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"rank {rank} is not in a world of {world}")
+        unsupported = [name for name, on in (("a BC term", bc is not None), ("dist_info", bool(dist_info)),
+                                             ("a subsampled Fisher (hvp_sample_frac < 0.99 or idx)", sub),
+                                             ("eval_before", self.eval_before),
+                                             ("cg_fold = False", not self.cg_fold)) if on]
+        if unsupported:
+            raise NotImplementedError("the data-parallel NPG update does not support " + ", ".join(unsupported))
+        obs, act, adv = self._inputs(observations, actions, advantages)
+        c, dev = self.ctx, self.ctx.device
+        n = obs.shape[0]
+        counts = torch.zeros(world, dtype=torch.int64, device=dev)
+        counts[rank] = n
+        allreduce(counts)
+        counts_h = [int(v) for v in counts.tolist()]
+        empty = [r for r, v in enumerate(counts_h) if v <= 0]
+        if empty:  # decided from the exchanged counts: the same error on every rank, no collective left open
+            raise ValueError(f"rank {empty[0]} of {world} holds no rows (row counts {counts_h}): every rank of a "
+                             "data-parallel NPG update needs at least one")
+        n_total = sum(counts_h)
+        if whiten:
+            wmsg = torch.zeros(world, 4, dtype=torch.float64, device=dev)
+            N.check(c.lib.amx_adv_whiten_parts(c.h, 1, n, None, None, n, adv.data_ptr(), rank, world, wmsg.data_ptr(),
+                                               c.stream), "amx_adv_whiten_parts")
+            allreduce(wmsg)
+            w = torch.empty_like(adv)
+            stats = torch.empty(2, dtype=torch.float64, device=dev)
+            N.check(c.lib.amx_adv_whiten_apply(c.h, 1, n, None, None, n, adv.data_ptr(), wmsg.data_ptr(), world, 1e-6,
+                                               w.data_ptr(), stats.data_ptr(), c.stream), "amx_adv_whiten_apply")
+            adv = w
+        hc = self._hcache(n)
+        vpg = self._pass(NPG_VPG, obs, act, adv, None, hcache=hc, n_total=n_total)
+        allreduce(vpg)
+        npg = self._cg_solve_dp(obs, act, vpg, hc, n_total, allreduce)
+        new = torch.empty(self.P, dtype=torch.float32, device=dev)
+        res = torch.empty(5, dtype=torch.float64, device=dev)  # [alpha, n_step_size, gdot | surr, kl]
+        use_alpha = self.alpha is not None
+        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), self.theta.data_ptr(),
+                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
+                                         float(self.n_step_size), self.min_log_std, new.data_ptr(),
+                                         res[:3].data_ptr(), c.stream), "amx_npg_apply_step")
+        ev = res[3:]
+        self._pass(NPG_EVAL, obs, act, adv, new, out=ev, n_total=n_total)  # plain sums: the host divides
+        allreduce(ev)
+        self.theta = new
+        if self.policy is not None:
+            self.policy.sync_from(*self._layers_view())
+        alpha_h, delta_h, _, surr_h, kl_h = res.tolist()  # the update's second host sync (after the counts)
+        return {"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h, "surr_before": 0.0,
+                "surr_after": surr_h / n_total, "kl_dist": kl_h / n_total, "advantages": adv, "n_total": n_total}
+
+    def train_from_paths(self, paths, infos: dict | None = None, *, allreduce=None, rank: int = 0,
+                         world: int = 1):
         """Reference surface: mjrl path dicts (observations, actions, advantages, rewards) ->
-        base_stats [mean, std, min, max] of path returns; infos updated as the reference's."""
+        base_stats [mean, std, min, max] of path returns; infos updated as the reference's.
+        `allreduce`, `rank`, `world`: train_from_arrays' (the paths are this rank's; the returned
+        statistics too)."""
         obs = np.concatenate([p["observations"] for p in paths])
         act = np.concatenate([p["actions"] for p in paths])
         adv = np.concatenate([p["advantages"] for p in paths])
-        out = self.train_from_arrays(obs, act, adv)
+        out = self.train_from_arrays(obs, act, adv, allreduce=allreduce, rank=rank, world=world)
         if infos is not None:
             infos.update({k: v for k, v in out.items()})
         returns = [float(np.sum(p["rewards"])) for p in paths]
         return [float(np.mean(returns)), float(np.std(returns)), float(np.min(returns)), float(np.max(returns))]
 
-    def train_from_engine(self, engine, advantages: torch.Tensor) -> dict:
+    def train_from_engine(self, engine, advantages: torch.Tensor, *, allreduce=None, rank: int = 0,
+                          world: int = 1) -> dict:
         """Update from the rollout engine's buffers without a host round trip: the recorded
-        transitions obs[:T], acts[:T] ([T, B] rows) and GAE advantages [T, B]."""
+        transitions obs[:T], acts[:T] ([T, B] rows) and GAE advantages [T, B].  `allreduce`, `rank`,
+        `world`: train_from_arrays' (the engine's lanes are this rank's shard of the rollout)."""
         T, B = engine.t, engine.B
         obs = engine.obs[:T].reshape(T * B, self.S)
         act = engine.acts[:T].reshape(T * B, self.A)
-        return self.train_from_arrays(obs, act, advantages.reshape(T * B))
+        return self.train_from_arrays(obs, act, advantages.reshape(T * B), allreduce=allreduce, rank=rank,
+                                      world=world)
 
 
 class NPG:
@@ -533,12 +681,17 @@ class NPG:
     attributes, `train_from_paths(paths, infos)` and logger.  `policy`: an mjrl MLP or any object
     with its attribute layout (see ppo.PPO).  `ctx`: the AmxContext to run on (one is made for the
     policy's sizes when None).  train_step and the rollout statistics come from the reference's
-    BatchREINFORCE: `class NPG(amx.NPG, BatchREINFORCE): pass`."""
+    BatchREINFORCE: `class NPG(amx.NPG, BatchREINFORCE): pass`.  `allreduce` (keyword-only): the
+    in-place SUM over the ranks of a sharded rollout (dist.allreduce_sum); the update is then the
+    data-parallel one over every rank's paths (DeviceNPG._train_dp), the advantages whitened on the
+    device with the ranks' joint statistics, without a BC term, a subsampled Fisher or the dist-info
+    entries of `infos`."""
 
     def __init__(self, env, policy, baseline, normalized_step_size=0.01, const_learn_rate=None,
                  FIM_invert_args={'iters': 10, 'damping': 1e-4}, hvp_sample_frac=1.0, seed=123, save_logs=False,
                  kl_dist=None, input_normalization=None,
-                 bc_args={'flag': False, 'expert_paths': None, 'reg_coeff': None}, ctx=None, **kwargs):
+                 bc_args={'flag': False, 'expert_paths': None, 'reg_coeff': None}, ctx=None, *, allreduce=None,
+                 **kwargs):
         from .bc import HIDDEN, DataLog
         tr = getattr(policy.model, "transformations", None)
         if tr and any(x is not None for x in tr.values()):
@@ -564,6 +717,9 @@ class NPG:
         self.input_normalization = None
         self.bc_args = bc_args
         self.ctx = ctx
+        # data-parallel: `paths` are this rank's, the update the union's (DeviceNPG._train_dp; rank and
+        # world from torch.distributed's group); running_score and the rollout statistics stay per rank
+        self.allreduce = allreduce
         self.device_npg = None
         self._expert = None  # (host obs, host act, device obs, device act)
 
@@ -581,7 +737,7 @@ class NPG:
         d = self.device_npg
         d.alpha, d.n_step_size, d.hvp_subsample = self.alpha, self.n_step_size, self.hvp_subsample
         d.cg_iters, d.damping = int(self.FIM_invert_args["iters"]), float(self.FIM_invert_args["damping"])
-        d.dist_info = d.eval_before = True
+        d.dist_info = d.eval_before = self.allreduce is None  # (not part of the data-parallel update)
         return d
 
     def _bc(self, d: DeviceNPG):
@@ -602,7 +758,8 @@ class NPG:
         observations = np.concatenate([path["observations"] for path in paths])
         actions = np.concatenate([path["actions"] for path in paths])
         advantages = np.concatenate([path["advantages"] for path in paths])
-        advantages = (advantages - np.mean(advantages)) / (np.std(advantages) + 1e-6)
+        if self.allreduce is None:  # (data-parallel: whitened on the device with the ranks' joint statistics)
+            advantages = (advantages - np.mean(advantages)) / (np.std(advantages) + 1e-6)
         path_returns = [sum(p["rewards"]) for p in paths]
         mean_return = np.mean(path_returns)
         base_stats = [mean_return, np.std(path_returns), np.amin(path_returns), np.amax(path_returns)]
@@ -621,16 +778,21 @@ class NPG:
         ts = timer.time()
         d = self._device_npg()
         d.theta = torch.from_numpy(np.asarray(cur, dtype=np.float32)).to(d.ctx.device)  # as the policy holds them
-        out = d.train_from_arrays(observations, actions, advantages, whiten=False, bc=self._bc(d))
+        dp = self.allreduce is not None
+        out = d.train_from_arrays(observations, actions, advantages, whiten=dp, bc=self._bc(d),
+                                  allreduce=self.allreduce)
         new_params = d.theta.cpu().numpy()
         pol.set_param_values(new_params, set_new=True, set_old=True)
         t_upd = timer.time() - ts
+        if dp:  # this rank's rows, whitened over all ranks; no per-row dist-info entries
+            infos['advantages'] = out["advantages"].cpu().numpy()
 
         f32 = np.float32
         surr_before, surr_after, kl_dist = f32(out["surr_before"]), f32(out["surr_after"]), f32(out["kl_dist"])
-        infos['old_dist_info'] = [t.cpu() for t in out["old_dist_info"]]
-        infos['new_dist_info'] = [t.cpu() for t in out["new_dist_info"]]
-        infos['lr'] = out["lr"].cpu()
+        if not dp:
+            infos['old_dist_info'] = [t.cpu() for t in out["old_dist_info"]]
+            infos['new_dist_info'] = [t.cpu() for t in out["new_dist_info"]]
+            infos['lr'] = out["lr"].cpu()
         infos['surr_before'] = surr_before
         if self.alpha is None:  # (npg_cg.py:157-161)
             infos['vpg_grad'] = out["vpg_grad"].cpu().numpy().astype(f32)

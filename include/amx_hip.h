@@ -397,6 +397,17 @@ int amx_npg_reduce_gated(amx_ctx* ctx, const double* partials, int blocks, int P
 int amx_npg_pass_ex(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, long long ldo, const void* act,
                     int act_dtype, long long lda, const double* adv, const float* theta, const float* vec,
                     int rows_per_block, double* partials, const double* gate, float* hcache, void* stream);
+/* amx_npg_pass_ex for one rank of a data-parallel update: the N rows are this rank's share of
+ * n_total rows held over all ranks, and the means divide by n_total (VPG: adv / n_total; FVP:
+ * J^T D J / n_total), so the ranks' column sums add up to the gradient / Fisher-vector product of
+ * the union.  Blocks, row bounds and the hcache are the rank's own (N, rows_per_block); the EVAL
+ * partials are plain sums and do not depend on n_total.  n_total == N is amx_npg_pass_ex bit for
+ * bit; a power-of-two ratio scales every VPG / FVP partial exactly.  n_total < N or < 1:
+ * AMX_E_ARG, nothing launched. */
+int amx_npg_pass_dp(amx_ctx* ctx, int mode, int N, const void* obs, int obs_dtype, long long ldo, const void* act,
+                    int act_dtype, long long lda, const double* adv, const float* theta, const float* vec,
+                    int rows_per_block, double* partials, const double* gate, float* hcache, long long n_total,
+                    void* stream);
 
 /* The conjugate-gradient solve of NPG (mjrl/mjrl/utils/cg_solve.py:3-23) on the device, one
  * workgroup per call, fixed-order fp64 reductions, no host round trip between iterations.
@@ -453,6 +464,20 @@ int amx_npg_pass_cg(amx_ctx* ctx, int N, const void* obs, int obs_dtype, long lo
                     int rows_per_block, double* partials, float* hcache, double tol, double* x, const double* r_in,
                     double* r_out, const double* p_in, double* p_out, float* p32_out, const double* state_in,
                     double* state_out, const double* work, void* stream);
+/* amx_npg_pass_cg with amx_npg_pass_dp's divisor: one rank's Fisher-vector pass of a data-parallel
+ * solve.  The rank's message of the iteration is amx_npg_reduce_gated(partials, blocks, P, msg,
+ * state_out): its column sums as one [P] vector, left alone once the solve has stopped; the caller
+ * sums msg over the ranks and hands it to amx_npg_cg_reduce as a one-block partials buffer
+ * (blocks = 1: h = msg, the sum of one run of one block).  The fold reads only work, r, p and the
+ * state, which are formed from the summed message, so every rank takes the same vector step bit
+ * for bit provided the collective leaves the same bits on every rank.  With one rank and no
+ * collective the message path gives amx_npg_cg_reduce's bits over the partials themselves (the
+ * amx_npg_reduce order).  n_total < N or < 1: AMX_E_ARG, nothing launched. */
+int amx_npg_pass_cg_dp(amx_ctx* ctx, int N, const void* obs, int obs_dtype, long long ldo, const float* theta,
+                       int rows_per_block, double* partials, float* hcache, double tol, double* x,
+                       const double* r_in, double* r_out, const double* p_in, double* p_out, float* p32_out,
+                       const double* state_in, double* state_out, const double* work, long long n_total,
+                       void* stream);
 /* The Fisher-vector pass over an index vector: NPG.HVP with hvp_sample_frac < 1
  * (mjrl/mjrl/algos/npg_cg.py:90-94).  row_idx: device int32 [M], 0 <= row_idx[k] < N (the caller
  * guarantees the range; duplicates are legal, the reference samples with replacement).  The pass
@@ -779,6 +804,22 @@ int amx_gae(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base,
 int amx_adv_whiten(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base,
                    long long stride, const double* adv, double eps, double* out, double* stats,
                    void* stream);
+/* amx_adv_whiten in two halves, for rows sharded over `world` ranks (statistics over the union).
+ * amx_adv_whiten_parts: the rank's rows -> one record {count, mean, M2, residual} in slot `rank`
+ * of msg (device fp64 [world][4], zeroed by the caller, so a SUM all-reduce over the ranks is an
+ * all-gather): amx_adv_whiten's per-block parts in its block order, combined as it combines them
+ * (mean and M2 about that mean as amx_adv_whiten's stats hold them); residual = what the mean's
+ * rounding left of the rank's sum, kept only as far as mean + residual / count == mean.
+ * amx_adv_whiten_apply: combines the `world` records in rank order with the same combine (the
+ * apply kernel of amx_adv_whiten, its parts read from msg), writes stats = {mean, std} and
+ * out = (adv - mean) / (std + eps) for the local rows.  world == 1 gives amx_adv_whiten's stats and
+ * rows bit for bit.  Same context scratch as amx_adv_whiten (one whitening at a time);
+ * 1 <= world <= 1024, 0 <= rank < world. */
+int amx_adv_whiten_parts(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base, long long stride,
+                         const double* adv, int rank, int world, double* msg, void* stream);
+int amx_adv_whiten_apply(amx_ctx* ctx, int T, int L, const int32_t* len, const int64_t* base, long long stride,
+                         const double* adv, const double* msg, int world, double eps, double* out, double* stats,
+                         void* stream);
 
 /* ---- fitting the value baseline (MLPBaseline.fit) ------------------------------ */
 
