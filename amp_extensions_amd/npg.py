@@ -34,6 +34,7 @@ import torch
 
 from . import _native as N
 from .engine import AmxContext
+from .gae import whiten_grid
 
 NPG_VPG, NPG_FVP, NPG_EVAL = 0, 1, 2
 
@@ -61,6 +62,22 @@ def unpack_policy(flat, S: int, A: int, hidden=(32, 32)):
         i += o
         layers.append((W, b))
     return layers, torch.from_numpy(flat[i:i + A].copy())
+
+
+def paths_to_arrays(paths):
+    """mjrl path dicts -> the concatenated observations, actions and advantages, and base_stats
+    [mean, std, min, max] of the path returns (DeviceNPG's and DevicePPO's train_from_paths)."""
+    obs, act, adv = (np.concatenate([p[k] for p in paths]) for k in ("observations", "actions", "advantages"))
+    returns = [float(np.sum(p["rewards"])) for p in paths]
+    return obs, act, adv, [float(np.mean(returns)), float(np.std(returns)), float(np.min(returns)),
+                           float(np.max(returns))]
+
+
+def engine_rows(engine, advantages: torch.Tensor, S: int, A: int):
+    """The rollout engine's recorded transitions obs[:T], acts[:T] and the GAE advantages [T, B] as
+    [T * B] rows, without a host round trip (DeviceNPG's and DevicePPO's train_from_engine)."""
+    T, B = engine.t, engine.B
+    return engine.obs[:T].reshape(T * B, S), engine.acts[:T].reshape(T * B, A), advantages.reshape(T * B)
 
 
 class DeviceNPG:
@@ -132,6 +149,14 @@ class DeviceNPG:
         # one block per CU (the pass kernel holds ~140 KB of LDS): one wave of blocks
         return max(32, int(math.ceil(n / 256 / 32)) * 32)
 
+    def _reduce(self, part, blocks: int, width: int, out, gate=None):
+        """out[width] = the column sums of the [blocks][width] partials in block order
+        (amx_npg_reduce_gated; behind `gate`, a stopped solve's state, it leaves `out` alone)."""
+        c = self.ctx
+        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), blocks, width, out.data_ptr(), N.ptr(gate), c.stream),
+                "amx_npg_reduce")
+        return out
+
     def _pass(self, mode, obs, act, adv, vec, gate=None, hcache=None, reduce=True, out=None, part=None,
               n_total=None):
         """One pass (amx_npg_pass_ex) and its block-order reduction (into `out` when given);
@@ -153,26 +178,17 @@ class DeviceNPG:
             part = self._bufs[key] = torch.empty(nb, width, dtype=torch.float64, device=c.device)
         od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
         ad = N.AMX_IN_F64 if act.dtype == torch.float64 else N.AMX_IN_F32
-        g = None if gate is None else gate.data_ptr()
+        args = (c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad, act.stride(0), N.ptr(adv),
+                self.theta.data_ptr(), N.ptr(vec), rpb, part.data_ptr(), N.ptr(gate), N.ptr(hcache))
         if n_total is None:
-            N.check(c.lib.amx_npg_pass_ex(c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad,
-                                          act.stride(0), None if adv is None else adv.data_ptr(),
-                                          self.theta.data_ptr(), None if vec is None else vec.data_ptr(), rpb,
-                                          part.data_ptr(), g, None if hcache is None else hcache.data_ptr(),
-                                          c.stream), "amx_npg_pass")
+            N.check(c.lib.amx_npg_pass_ex(*args, c.stream), "amx_npg_pass")
         else:
-            N.check(c.lib.amx_npg_pass_dp(c.h, mode, n, obs.data_ptr(), od, obs.stride(0), act.data_ptr(), ad,
-                                          act.stride(0), None if adv is None else adv.data_ptr(),
-                                          self.theta.data_ptr(), None if vec is None else vec.data_ptr(), rpb,
-                                          part.data_ptr(), g, None if hcache is None else hcache.data_ptr(),
-                                          int(n_total), c.stream), "amx_npg_pass_dp")
+            N.check(c.lib.amx_npg_pass_dp(*args, int(n_total), c.stream), "amx_npg_pass_dp")
         if not reduce:
             return part
         if out is None:
             out = torch.empty(width, dtype=torch.float64, device=c.device)
-        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), nb, width, out.data_ptr(), g, c.stream),
-                "amx_npg_reduce")
-        return out
+        return self._reduce(part, nb, width, out, gate)
 
     def _inputs(self, observations, actions, advantages=None):
         dev = self.ctx.device
@@ -233,17 +249,16 @@ class DeviceNPG:
                                  theta.data_ptr(), part.data_ptr(), N.ptr(ll), N.ptr(mean), c.stream), "amx_npg_ll")
         if out is None:
             out = torch.empty(1, dtype=torch.float64, device=c.device)
-        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), nb, 1, out.data_ptr(), None, c.stream),
-                "amx_npg_reduce")
+        self._reduce(part, nb, 1, out)
         return (out, ll, mean) if rows else out
 
-    def _vpg(self, obs, act, adv, hcache=None, bc=None) -> torch.Tensor:
+    def _vpg(self, obs, act, adv, hcache=None, bc=None, n_total=None) -> torch.Tensor:
         """The gradient of CPI_surrogate at new == old.  With a BC term: the rollout's VPG partials
         and those of the expert rows with every advantage equal to reg_coeff (the pass divides by
         its own N: reg_coeff * mean(LL)'s gradient) in one buffer, summed by one reduction, the
-        rollout's blocks first."""
+        rollout's blocks first.  `n_total`: _pass' (a data-parallel update takes no BC term)."""
         if bc is None:
-            return self._pass(NPG_VPG, obs, act, adv, None, hcache=hcache)
+            return self._pass(NPG_VPG, obs, act, adv, None, hcache=hcache, n_total=n_total)
         c = self.ctx
         eo, ea, reg = bc
         nb, nbe = (math.ceil(x.shape[0] / self._rows_per_block(x.shape[0])) for x in (obs, eo))
@@ -251,10 +266,7 @@ class DeviceNPG:
         self._pass(NPG_VPG, obs, act, adv, None, hcache=hcache, part=part[:nb])
         eadv = torch.full((eo.shape[0],), float(reg), dtype=torch.float64, device=c.device)
         self._pass(NPG_VPG, eo, ea, eadv, None, part=part[nb:])
-        out = torch.empty(self.P, dtype=torch.float64, device=c.device)
-        N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), nb + nbe, self.P, out.data_ptr(), None, c.stream),
-                "amx_npg_reduce")
-        return out
+        return self._reduce(part, nb + nbe, self.P, torch.empty(self.P, dtype=torch.float64, device=c.device))
 
     def _bc_inputs(self, bc):
         if bc is None:
@@ -292,9 +304,8 @@ class DeviceNPG:
             h = self._pass(NPG_FVP, obs, act, None, v32)
         else:
             part = self._pass_idx(obs, idx, v32)
-            h = torch.empty(self.P, dtype=torch.float64, device=self.ctx.device)
-            N.check(self.ctx.lib.amx_npg_reduce_gated(self.ctx.h, part.data_ptr(), part.shape[0], self.P,
-                                                      h.data_ptr(), None, self.ctx.stream), "amx_npg_reduce")
+            h = self._reduce(part, part.shape[0], self.P,
+                             torch.empty(self.P, dtype=torch.float64, device=self.ctx.device))
         h[-self.A:] += self._ls_curvature() * v32[-self.A:].double()
         return h + regu * v.to(torch.float64)  # hvp_flat + regu_coef * vector (npg_cg.py:105: the fp64 vector)
 
@@ -306,7 +317,8 @@ class DeviceNPG:
             hc = self._bufs["hcache"] = torch.empty(n, 64, dtype=torch.float32, device=self.ctx.device)
         return hc
 
-    def cg_solve(self, obs, act, b: torch.Tensor, hcache=None, idx=None, count=None) -> torch.Tensor:
+    def cg_solve(self, obs, act, b: torch.Tensor, hcache=None, idx=None, count=None, *, n_total=None,
+                 allreduce=None) -> torch.Tensor:
         """mjrl/mjrl/utils/cg_solve.py:3-23 (starts from zeros; stops at rdotr < tol) with
         NPG.HVP as the operator.  Each iteration is one Fisher-vector pass and one column-sum
         launch (amx_npg_cg_reduce: z and the p.z parts per block); the vector step (x, r, p from
@@ -320,10 +332,21 @@ class DeviceNPG:
         skips layers 1-2 at theta (bit-identical products).  `idx`: a device int32 [iters][M]
         table, iteration i's product on the rows obs[idx[i]] (NPG.HVP's subsampled Fisher, one
         draw per product); `count` (device fp64 [1], zeroed by the caller) then counts the
-        products taken, i.e. the draws the reference's loop makes before its break."""
+        products taken, i.e. the draws the reference's loop makes before its break.
+
+        `allreduce` (with `n_total`, the rows of every rank): one rank's solve of a data-parallel
+        update.  The passes divide by n_total (amx_npg_pass_dp, amx_npg_pass_cg_dp); the rank's
+        column sums leave as one [P] message (amx_npg_reduce_gated), are summed over the ranks, and
+        amx_npg_cg_reduce runs on the summed message as a one-block partials buffer: z, p.z and the
+        vector step are formed from the same bits on every rank.  The host cannot see the early
+        stop, so it always runs cg_iters collectives; a stopped solve (the same stop on every
+        rank) leaves the message alone: the collective then re-sums finite values nobody reads."""
         c = self.ctx
         P = self.P
         dev = c.device
+        fold = self.cg_fold
+        if allreduce is not None and (idx is not None or not fold):
+            raise NotImplementedError("the data-parallel solve is the folded one on all of the rank's rows")
         b = b.to(torch.float64).contiguous()
         if idx is not None:
             if idx.dim() != 2 or idx.shape[0] < self.cg_iters or idx.dtype != torch.int32 or not idx.is_contiguous():
@@ -334,6 +357,7 @@ class DeviceNPG:
         p32, p32b = (torch.empty(P, dtype=torch.float32, device=dev) for _ in range(2))
         state, state2 = (torch.empty(2, dtype=torch.float64, device=dev) for _ in range(2))
         curv = torch.empty(self.A, dtype=torch.float64, device=dev)  # the log_std curvature, same launch
+        msg = None if allreduce is None else torch.zeros(P, dtype=torch.float64, device=dev)
         N.check(c.lib.amx_npg_cg_init_ls(c.h, P, self.A, self.theta.data_ptr(), curv.data_ptr(), b.data_ptr(),
                                          x.data_ptr(), r.data_ptr(), p.data_ptr(), p32.data_ptr(), state.data_ptr(),
                                          c.stream), "amx_npg_cg_init_ls")
@@ -342,50 +366,47 @@ class DeviceNPG:
             work = self._bufs["cg_work"] = torch.empty(int(c.lib.amx_npg_cg_tail_work(P)), dtype=torch.float64,
                                                        device=dev)
         hc = hcache if obs.dtype == torch.float32 else None
-        if not self.cg_fold:
-            for it in range(self.cg_iters):
+        n = obs.shape[0]
+        rpb = self._rows_per_block(n if idx is None else idx.shape[1])
+        od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
+        for it in range(self.cg_iters):
+            if it == 0 or not fold:  # the product with p32 alone
                 if idx is None:
-                    part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False)
+                    part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False,
+                                      n_total=n_total)
                 else:
                     part = self._pass_idx(obs, idx[it], p32, gate=state, hcache=hc, count=count)
+            else:
+                # the previous iteration's vector step, then the product with its p'; r, p, p32
+                # and the state alternate buffers (every block reads all of them)
+                args = (obs.data_ptr(), od, obs.stride(0), self.theta.data_ptr(), rpb, part.data_ptr(), N.ptr(hc),
+                        self.residual_tol, x.data_ptr(), r.data_ptr(), r2.data_ptr(), p.data_ptr(), p2.data_ptr(),
+                        p32b.data_ptr(), state.data_ptr(), state2.data_ptr(), work.data_ptr())
+                if idx is not None:
+                    N.check(c.lib.amx_npg_pass_cg_idx(c.h, n, idx.shape[1], idx[it].data_ptr(), *args, N.ptr(count),
+                                                      c.stream), "amx_npg_pass_cg_idx")
+                elif n_total is None:
+                    N.check(c.lib.amx_npg_pass_cg(c.h, n, *args, c.stream), "amx_npg_pass_cg")
+                else:
+                    N.check(c.lib.amx_npg_pass_cg_dp(c.h, n, *args, int(n_total), c.stream), "amx_npg_pass_cg_dp")
+                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
+            if not fold:
                 # the partials' column sums and the vector step (amx_npg_cg_tail: two launches); r
                 # and the state alternate buffers from one iteration to the next
                 N.check(c.lib.amx_npg_cg_tail(c.h, part.data_ptr(), part.shape[0], P, self.A, curv.data_ptr(),
                                               self.damping, self.residual_tol, x.data_ptr(), r.data_ptr(),
                                               r2.data_ptr(), p.data_ptr(), p32.data_ptr(), state.data_ptr(),
                                               state2.data_ptr(), work.data_ptr(), c.stream), "amx_npg_cg_tail")
-                r, r2 = r2, r
-                state, state2 = state2, state
-            return x
-        n = obs.shape[0]
-        rpb = self._rows_per_block(n if idx is None else idx.shape[1])
-        od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
-        for it in range(self.cg_iters):
-            if it == 0 and idx is None:
-                part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False)
-            elif it == 0:
-                part = self._pass_idx(obs, idx[0], p32, gate=state, hcache=hc, count=count)
-            elif idx is not None:
-                N.check(c.lib.amx_npg_pass_cg_idx(c.h, n, idx.shape[1], idx[it].data_ptr(), obs.data_ptr(), od,
-                                                  obs.stride(0), self.theta.data_ptr(), rpb, part.data_ptr(),
-                                                  N.ptr(hc), self.residual_tol, x.data_ptr(), r.data_ptr(),
-                                                  r2.data_ptr(), p.data_ptr(), p2.data_ptr(), p32b.data_ptr(),
-                                                  state.data_ptr(), state2.data_ptr(), work.data_ptr(), N.ptr(count),
-                                                  c.stream), "amx_npg_pass_cg_idx")
-                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
-            else:
-                # the previous iteration's vector step, then the product with its p'; r, p, p32
-                # and the state alternate buffers (every block reads all of them)
-                N.check(c.lib.amx_npg_pass_cg(c.h, n, obs.data_ptr(), od, obs.stride(0), self.theta.data_ptr(), rpb,
-                                              part.data_ptr(), None if hc is None else hc.data_ptr(),
-                                              self.residual_tol, x.data_ptr(), r.data_ptr(), r2.data_ptr(),
-                                              p.data_ptr(), p2.data_ptr(), p32b.data_ptr(), state.data_ptr(),
-                                              state2.data_ptr(), work.data_ptr(), c.stream), "amx_npg_pass_cg")
-                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
-            N.check(c.lib.amx_npg_cg_reduce(c.h, part.data_ptr(), part.shape[0], P, self.A, curv.data_ptr(),
-                                            self.damping, p.data_ptr(), p32.data_ptr(), state.data_ptr(),
-                                            work.data_ptr(), c.stream), "amx_npg_cg_reduce")
-        if self.cg_iters > 0:
+                r, r2, state, state2 = r2, r, state2, state
+                continue
+            z, blocks = part, part.shape[0]
+            if allreduce is not None:  # the rank's column sums, summed over the ranks: one block
+                allreduce(self._reduce(part, blocks, P, msg, gate=state))
+                z, blocks = msg, 1
+            N.check(c.lib.amx_npg_cg_reduce(c.h, z.data_ptr(), blocks, P, self.A, curv.data_ptr(), self.damping,
+                                            p.data_ptr(), p32.data_ptr(), state.data_ptr(), work.data_ptr(),
+                                            c.stream), "amx_npg_cg_reduce")
+        if fold and self.cg_iters > 0:
             N.check(c.lib.amx_npg_cg_xrp(c.h, P, self.residual_tol, x.data_ptr(), r.data_ptr(), r2.data_ptr(),
                                          p.data_ptr(), p32.data_ptr(), state.data_ptr(), state2.data_ptr(),
                                          work.data_ptr(), c.stream), "amx_npg_cg_xrp")
@@ -411,6 +432,36 @@ class DeviceNPG:
             states.append(np.random.get_state())
         return np.asarray(rows, dtype=np.int32).reshape(self.cg_iters, m), states
 
+    def _whiten(self, adv, allreduce=None, rank: int = 0, world: int = 1) -> torch.Tensor:
+        """(adv - mean) / (std + 1e-6), population std (batch_reinforce.py:284-285): amx_adv_whiten,
+        or over the ranks' rows its two halves around the all-reduce of the [world][4] records."""
+        c = self.ctx
+        n = adv.numel()
+        w = torch.empty_like(adv)
+        if allreduce is None:
+            return whiten_grid(c, 1, n, adv, n, eps=1e-6, out=w)[0]
+        wmsg = torch.zeros(world, 4, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_adv_whiten_parts(c.h, 1, n, None, None, n, adv.data_ptr(), rank, world, wmsg.data_ptr(),
+                                           c.stream), "amx_adv_whiten_parts")
+        allreduce(wmsg)
+        stats = torch.empty(2, dtype=torch.float64, device=c.device)
+        N.check(c.lib.amx_adv_whiten_apply(c.h, 1, n, None, None, n, adv.data_ptr(), wmsg.data_ptr(), world, 1e-6,
+                                           w.data_ptr(), stats.data_ptr(), c.stream), "amx_adv_whiten_apply")
+        return w
+
+    def _apply_step(self, vpg, npg, res) -> torch.Tensor:
+        """gdot, the step size and the clamped new parameters in one launch (amx_npg_apply_step):
+        res[:3] = [alpha, n_step_size, gdot]; returns the new theta, already float32 with the
+        log_std clamp (set_param_values' form)."""
+        c = self.ctx
+        new = torch.empty(self.P, dtype=torch.float32, device=c.device)
+        use_alpha = self.alpha is not None
+        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), self.theta.data_ptr(),
+                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
+                                         float(self.n_step_size), self.min_log_std, new.data_ptr(), res.data_ptr(),
+                                         c.stream), "amx_npg_apply_step")
+        return new
+
     def train_from_arrays(self, observations, actions, advantages, whiten: bool = True, bc=None,
                           dist_info=None, idx=None, *, allreduce=None, rank: int = 0, world: int = 1) -> dict:
         """NPG.train_from_paths on concatenated arrays (npg_cg.py:113-199): whitening
@@ -423,58 +474,58 @@ class DeviceNPG:
         the old, where the reference's last CPI_surrogate call takes them.  `idx`: the
         [cg_iters][M] rows of the subsampled Fisher; by default, with hvp_sample_frac < 0.99, they
         are drawn as the reference draws them and numpy's generator is left after as many draws
-        as the solve took products.  With none of these the update is the plain one.
+        as the solve took products.  Any of these, or `eval_before`, also computes surr_before and
+        returns hvp_products; with none the update is the plain one (surr_before 0.0): the same
+        launches in the same order, less theirs.
 
         `allreduce` (with `rank`, `world`; taken from torch.distributed's group when one is
-        initialised): the rows are this rank's share of a data-parallel update over `world` ranks
-        (see _train_dp); `allreduce(t)` sums a device tensor in place over the ranks, as
-        RolloutEngine.relabel's.  None: the single-process update, unchanged."""
+        initialised): the rows are this rank's share of a data-parallel update over `world` ranks,
+        the update is the union's; `allreduce(t)` sums a device tensor in place over the ranks, as
+        RolloutEngine.relabel's.  None: the single-process update.  The collectives of one update,
+        in this order on every rank (each on the context's stream order):
+          1. the row counts, int64 [world] (slot `rank` = the local n; the one extra host sync);
+          2. the whitening records, fp64 [world][4] (only with `whiten`);
+          3. the VPG, fp64 [P];
+          4. cg_iters messages, fp64 [P] (see cg_solve);
+          5. the EVAL sums, fp64 [2].
+        Every pass divides by the global count; vpg_grad, npg_grad, alpha, delta, the new theta,
+        surr_after and kl_dist are global and, given a collective that leaves the same bits on
+        every rank, identical on all of them; `advantages` are the rank's own rows whitened with
+        the global statistics.  A rank without rows makes every rank raise the same ValueError
+        after the count exchange; a BC term, a subsampled Fisher, dist_info or eval_before raise
+        NotImplementedError before any collective (numpy's draw order has no multi-rank meaning)."""
         bc = self.bc if bc is None else bc
         dist_info = self.dist_info if dist_info is None else dist_info
         sub = idx is not None or (self.hvp_subsample is not None and self.hvp_subsample < 0.99)
-        if allreduce is not None:
-            return self._train_dp(observations, actions, advantages, whiten, bc, dist_info, sub, allreduce, rank,
-                                  world)
-        if bc is not None or dist_info or sub or self.eval_before:
-            return self._train_ext(observations, actions, advantages, whiten, bc, dist_info, idx, sub)
-        obs, act, adv = self._inputs(observations, actions, advantages)
-        c = self.ctx
-        n = obs.shape[0]
-        if whiten:  # (adv - mean) / (std + 1e-6), population std: amx_adv_whiten (per-block parts, then combine + apply)
-            w = torch.empty_like(adv)
-            stats = torch.empty(2, dtype=torch.float64, device=c.device)
-            N.check(c.lib.amx_adv_whiten(c.h, 1, n, None, None, n, adv.data_ptr(), 1e-6, w.data_ptr(),
-                                         stats.data_ptr(), c.stream), "amx_adv_whiten")
-            adv = w
-        hc = self._hcache(n)
-        vpg = self._pass(NPG_VPG, obs, act, adv, None, hcache=hc)
-        npg = self.cg_solve(obs, act, vpg, hcache=hc)
-        # gdot, the step size and the clamped new parameters in one launch (amx_npg_apply_step)
-        new = torch.empty(self.P, dtype=torch.float32, device=c.device)
-        # [alpha, n_step_size, gdot | surr, kl]: the step kernel and the eval reduction write the
-        # two ends of one buffer, read back in one copy (no concatenation kernel)
-        res = torch.empty(5, dtype=torch.float64, device=c.device)
-        scal = res[:3]
-        use_alpha = self.alpha is not None
-        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), self.theta.data_ptr(),
-                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
-                                         float(self.n_step_size), self.min_log_std, new.data_ptr(),
-                                         scal.data_ptr(), c.stream), "amx_npg_apply_step")
-        self._pass(NPG_EVAL, obs, act, adv, new, out=res[3:])
-        self.theta = new  # already float32 with the log_std clamp (set_param_values' form)
-        if self.policy is not None:
-            self.policy.sync_from(*self._layers_view())
-        # the update's one host sync: the reference's infos are python floats
-        alpha_h, delta_h, _, surr_h, kl_h = res.tolist()
-        return {"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h, "surr_before": 0.0,
-                "surr_after": surr_h / n, "kl_dist": kl_h / n, "advantages": adv}
-
-    def _train_ext(self, observations, actions, advantages, whiten, bc, dist_info, idx, sub) -> dict:
-        """train_from_arrays with a BC term, a subsampled Fisher, the dist-info entries or a
-        computed surr_before: the same launches in the same order, plus theirs."""
+        ext = bc is not None or dist_info or sub or self.eval_before
+        dp = allreduce is not None
+        if dp:
+            from . import dist as D
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                rank, world = D.rank_world()
+            rank, world = int(rank), int(world)
+            if world < 1 or not 0 <= rank < world:
+                raise ValueError(f"rank {rank} is not in a world of {world}")
+            unsupported = [name for name, on in (("a BC term", bc is not None), ("dist_info", bool(dist_info)),
+                                                 ("a subsampled Fisher (hvp_sample_frac < 0.99 or idx)", sub),
+                                                 ("eval_before", self.eval_before),
+                                                 ("cg_fold = False", not self.cg_fold)) if on]
+            if unsupported:
+                raise NotImplementedError("the data-parallel NPG update does not support " + ", ".join(unsupported))
         obs, act, adv = self._inputs(observations, actions, advantages)
         c, dev = self.ctx, self.ctx.device
         n = obs.shape[0]
+        n_total = None  # the passes' divisor when it is not their own n
+        if dp:
+            counts = torch.zeros(world, dtype=torch.int64, device=dev)
+            counts[rank] = n
+            allreduce(counts)
+            counts_h = [int(v) for v in counts.tolist()]
+            empty = [r for r, v in enumerate(counts_h) if v <= 0]
+            if empty:  # decided from the exchanged counts: the same error on every rank, no collective left open
+                raise ValueError(f"rank {empty[0]} of {world} holds no rows (row counts {counts_h}): every rank of a "
+                                 "data-parallel NPG update needs at least one")
+            n_total = sum(counts_h)
         bc = self._bc_inputs(bc)
         states = None
         if sub and self.cg_iters > 0:
@@ -486,28 +537,29 @@ class DeviceNPG:
         else:
             idx = None
         if whiten:
-            w = torch.empty_like(adv)
-            stats = torch.empty(2, dtype=torch.float64, device=dev)
-            N.check(c.lib.amx_adv_whiten(c.h, 1, n, None, None, n, adv.data_ptr(), 1e-6, w.data_ptr(),
-                                         stats.data_ptr(), c.stream), "amx_adv_whiten")
-            adv = w
-        # [alpha, n_step_size, gdot | surr_after, kl | surr_before, kl_before | products |
-        #  sum LL(expert) at the old, at the new parameters]: one buffer, read back in one copy
-        res = torch.zeros(10, dtype=torch.float64, device=dev)
+            adv = self._whiten(adv, allreduce, rank, world)
+        # [alpha, n_step_size, gdot | surr_after, kl], then only with `ext`, zeroed: [surr_before,
+        # kl_before | products | sum LL(expert) at the old, at the new parameters]: the kernels write
+        # the parts of one buffer, read back in one copy (no concatenation kernel)
+        res = torch.zeros(10, dtype=torch.float64, device=dev) if ext else \
+            torch.empty(5, dtype=torch.float64, device=dev)
         old = self.theta
         hc = self._hcache(n)
-        vpg = self._vpg(obs, act, adv, hcache=hc, bc=bc)
-        self._pass(NPG_EVAL, obs, act, adv, old, out=res[5:7])  # new == old: LR == 1 on every row
-        if bc is not None:
-            self.log_likelihood(bc[0], bc[1], old, out=res[8:9])
-        npg = self.cg_solve(obs, act, vpg, hcache=hc, idx=idx, count=res[7:8])
-        new = torch.empty(self.P, dtype=torch.float32, device=dev)
-        use_alpha = self.alpha is not None
-        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), old.data_ptr(),
-                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
-                                         float(self.n_step_size), self.min_log_std, new.data_ptr(),
-                                         res[:3].data_ptr(), c.stream), "amx_npg_apply_step")
-        self._pass(NPG_EVAL, obs, act, adv, new, out=res[3:5])
+        vpg = self._vpg(obs, act, adv, hcache=hc, bc=bc, n_total=n_total)
+        if dp:
+            allreduce(vpg)
+        count = None
+        if ext:
+            count = res[7:8]
+            self._pass(NPG_EVAL, obs, act, adv, old, out=res[5:7])  # new == old: LR == 1 on every row
+            if bc is not None:
+                self.log_likelihood(bc[0], bc[1], old, out=res[8:9])
+        npg = self.cg_solve(obs, act, vpg, hcache=hc, idx=idx, count=count, n_total=n_total, allreduce=allreduce)
+        new = self._apply_step(vpg, npg, res)
+        ev = res[3:5]
+        self._pass(NPG_EVAL, obs, act, adv, new, out=ev, n_total=n_total)  # plain sums: the host divides
+        if dp:
+            allreduce(ev)
         if bc is not None:
             self.log_likelihood(bc[0], bc[1], new, out=res[9:10])
         out = {}
@@ -519,135 +571,24 @@ class DeviceNPG:
         self.theta = new
         if self.policy is not None:
             self.policy.sync_from(*self._layers_view())
-        alpha_h, delta_h, _, surr_h, kl_h, sb_h, _, count_h, lle_o, lle_n = res.tolist()  # the one host sync
-        self.hvp_products = int(count_h) if idx is not None else 0
-        if states is not None:  # the reference's loop stops drawing at its break (cg_solve.py:19-20)
-            np.random.set_state(states[self.hvp_products])
-        reg, ne = (bc[2], bc[0].shape[0]) if bc is not None else (0.0, 1)
-        out.update({"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h,
-                    "surr_before": sb_h / n + reg * lle_o / ne, "surr_after": surr_h / n + reg * lle_n / ne,
-                    "kl_dist": kl_h / n, "advantages": adv, "hvp_products": self.hvp_products})
+        # the update's one host sync (after the counts' when data-parallel): the reference's infos
+        # are python floats
+        vals = res.tolist()
+        alpha_h, delta_h, _, surr_h, kl_h = vals[:5]
+        rows = n if n_total is None else n_total
+        out.update({"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h, "surr_before": 0.0,
+                    "surr_after": surr_h / rows, "kl_dist": kl_h / rows, "advantages": adv})
+        if ext:
+            sb_h, _, count_h, lle_o, lle_n = vals[5:]
+            self.hvp_products = int(count_h) if idx is not None else 0
+            if states is not None:  # the reference's loop stops drawing at its break (cg_solve.py:19-20)
+                np.random.set_state(states[self.hvp_products])
+            reg, ne = (bc[2], bc[0].shape[0]) if bc is not None else (0.0, 1)
+            out.update({"surr_before": sb_h / n + reg * lle_o / ne, "surr_after": surr_h / n + reg * lle_n / ne,
+                        "hvp_products": self.hvp_products})
+        if dp:
+            out["n_total"] = n_total
         return out
-
-    # ---- the data-parallel update ----------------------------------------------------------
-    def _cg_solve_dp(self, obs, act, b: torch.Tensor, hcache, n_total: int, allreduce) -> torch.Tensor:
-        """cg_solve's folded form for one rank of a data-parallel update.  Per iteration: the
-        Fisher-vector pass over the rank's rows divided by n_total (amx_npg_pass_dp on p32, then
-        amx_npg_pass_cg_dp with the previous vector step folded in), the rank's column sums as one
-        [P] message (amx_npg_reduce_gated), `allreduce`, and amx_npg_cg_reduce on the summed message
-        as a one-block partials buffer: z, p.z and the vector step are formed from the same bits on
-        every rank.  The host cannot see the early stop, so it always runs cg_iters collectives; a
-        stopped solve (the same stop on every rank) leaves the message alone: the collective then
-        re-sums finite values nobody reads."""
-        c, P, dev = self.ctx, self.P, self.ctx.device
-        b = b.to(torch.float64).contiguous()
-        x, r, p, r2, p2 = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(5))
-        p32, p32b = (torch.empty(P, dtype=torch.float32, device=dev) for _ in range(2))
-        state, state2 = (torch.empty(2, dtype=torch.float64, device=dev) for _ in range(2))
-        curv = torch.empty(self.A, dtype=torch.float64, device=dev)
-        msg = torch.zeros(P, dtype=torch.float64, device=dev)
-        N.check(c.lib.amx_npg_cg_init_ls(c.h, P, self.A, self.theta.data_ptr(), curv.data_ptr(), b.data_ptr(),
-                                         x.data_ptr(), r.data_ptr(), p.data_ptr(), p32.data_ptr(), state.data_ptr(),
-                                         c.stream), "amx_npg_cg_init_ls")
-        work = self._bufs.get("cg_work")
-        if work is None:
-            work = self._bufs["cg_work"] = torch.empty(int(c.lib.amx_npg_cg_tail_work(P)), dtype=torch.float64,
-                                                       device=dev)
-        hc = hcache if obs.dtype == torch.float32 else None
-        n = obs.shape[0]
-        rpb = self._rows_per_block(n)
-        od = N.AMX_IN_F64 if obs.dtype == torch.float64 else N.AMX_IN_F32
-        for it in range(self.cg_iters):
-            if it == 0:
-                part = self._pass(NPG_FVP, obs, act, None, p32, gate=state, hcache=hc, reduce=False, n_total=n_total)
-            else:
-                N.check(c.lib.amx_npg_pass_cg_dp(c.h, n, obs.data_ptr(), od, obs.stride(0), self.theta.data_ptr(), rpb,
-                                                 part.data_ptr(), N.ptr(hc), self.residual_tol, x.data_ptr(),
-                                                 r.data_ptr(), r2.data_ptr(), p.data_ptr(), p2.data_ptr(),
-                                                 p32b.data_ptr(), state.data_ptr(), state2.data_ptr(),
-                                                 work.data_ptr(), int(n_total), c.stream), "amx_npg_pass_cg_dp")
-                r, r2, p, p2, p32, p32b, state, state2 = r2, r, p2, p, p32b, p32, state2, state
-            N.check(c.lib.amx_npg_reduce_gated(c.h, part.data_ptr(), part.shape[0], P, msg.data_ptr(),
-                                               state.data_ptr(), c.stream), "amx_npg_reduce")
-            allreduce(msg)
-            N.check(c.lib.amx_npg_cg_reduce(c.h, msg.data_ptr(), 1, P, self.A, curv.data_ptr(), self.damping,
-                                            p.data_ptr(), p32.data_ptr(), state.data_ptr(), work.data_ptr(),
-                                            c.stream), "amx_npg_cg_reduce")
-        if self.cg_iters > 0:
-            N.check(c.lib.amx_npg_cg_xrp(c.h, P, self.residual_tol, x.data_ptr(), r.data_ptr(), r2.data_ptr(),
-                                         p.data_ptr(), p32.data_ptr(), state.data_ptr(), state2.data_ptr(),
-                                         work.data_ptr(), c.stream), "amx_npg_cg_xrp")
-        return x
-
-    def _train_dp(self, observations, actions, advantages, whiten, bc, dist_info, sub, allreduce, rank, world):
-        """train_from_arrays for one rank of a data-parallel update: the rows are this rank's
-        share, the update is the union's.  The collectives of one update, in this order on every
-        rank (each `allreduce(t)` on the context's stream order):
-          1. the row counts, int64 [world] (slot `rank` = the local n; the one extra host sync);
-          2. the whitening records, fp64 [world][4] (only with `whiten`);
-          3. the VPG, fp64 [P];
-          4. cg_iters messages, fp64 [P] (see _cg_solve_dp);
-          5. the EVAL sums, fp64 [2].
-        Every pass divides by the global count; vpg_grad, npg_grad, alpha, delta, the new theta,
-        surr_after and kl_dist are global and, given a collective that leaves the same bits on
-        every rank, identical on all of them; `advantages` are the rank's own rows whitened with
-        the global statistics.  A rank without rows makes every rank raise the same ValueError
-        after the count exchange; a BC term, a subsampled Fisher, dist_info or eval_before raise
-        NotImplementedError before any collective (numpy's draw order has no multi-rank meaning)."""
-        from . import dist as D
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank, world = D.rank_world()
-        rank, world = int(rank), int(world)
-        if world < 1 or not 0 <= rank < world:
-            raise ValueError(f"rank {rank} is not in a world of {world}")
-        unsupported = [name for name, on in (("a BC term", bc is not None), ("dist_info", bool(dist_info)),
-                                             ("a subsampled Fisher (hvp_sample_frac < 0.99 or idx)", sub),
-                                             ("eval_before", self.eval_before),
-                                             ("cg_fold = False", not self.cg_fold)) if on]
-        if unsupported:
-            raise NotImplementedError("the data-parallel NPG update does not support " + ", ".join(unsupported))
-        obs, act, adv = self._inputs(observations, actions, advantages)
-        c, dev = self.ctx, self.ctx.device
-        n = obs.shape[0]
-        counts = torch.zeros(world, dtype=torch.int64, device=dev)
-        counts[rank] = n
-        allreduce(counts)
-        counts_h = [int(v) for v in counts.tolist()]
-        empty = [r for r, v in enumerate(counts_h) if v <= 0]
-        if empty:  # decided from the exchanged counts: the same error on every rank, no collective left open
-            raise ValueError(f"rank {empty[0]} of {world} holds no rows (row counts {counts_h}): every rank of a "
-                             "data-parallel NPG update needs at least one")
-        n_total = sum(counts_h)
-        if whiten:
-            wmsg = torch.zeros(world, 4, dtype=torch.float64, device=dev)
-            N.check(c.lib.amx_adv_whiten_parts(c.h, 1, n, None, None, n, adv.data_ptr(), rank, world, wmsg.data_ptr(),
-                                               c.stream), "amx_adv_whiten_parts")
-            allreduce(wmsg)
-            w = torch.empty_like(adv)
-            stats = torch.empty(2, dtype=torch.float64, device=dev)
-            N.check(c.lib.amx_adv_whiten_apply(c.h, 1, n, None, None, n, adv.data_ptr(), wmsg.data_ptr(), world, 1e-6,
-                                               w.data_ptr(), stats.data_ptr(), c.stream), "amx_adv_whiten_apply")
-            adv = w
-        hc = self._hcache(n)
-        vpg = self._pass(NPG_VPG, obs, act, adv, None, hcache=hc, n_total=n_total)
-        allreduce(vpg)
-        npg = self._cg_solve_dp(obs, act, vpg, hc, n_total, allreduce)
-        new = torch.empty(self.P, dtype=torch.float32, device=dev)
-        res = torch.empty(5, dtype=torch.float64, device=dev)  # [alpha, n_step_size, gdot | surr, kl]
-        use_alpha = self.alpha is not None
-        N.check(c.lib.amx_npg_apply_step(c.h, self.P, self.A, vpg.data_ptr(), npg.data_ptr(), self.theta.data_ptr(),
-                                         int(use_alpha), float(self.alpha) if use_alpha else 0.0,
-                                         float(self.n_step_size), self.min_log_std, new.data_ptr(),
-                                         res[:3].data_ptr(), c.stream), "amx_npg_apply_step")
-        ev = res[3:]
-        self._pass(NPG_EVAL, obs, act, adv, new, out=ev, n_total=n_total)  # plain sums: the host divides
-        allreduce(ev)
-        self.theta = new
-        if self.policy is not None:
-            self.policy.sync_from(*self._layers_view())
-        alpha_h, delta_h, _, surr_h, kl_h = res.tolist()  # the update's second host sync (after the counts)
-        return {"vpg_grad": vpg, "npg_grad": npg, "alpha": alpha_h, "delta": delta_h, "surr_before": 0.0,
-                "surr_after": surr_h / n_total, "kl_dist": kl_h / n_total, "advantages": adv, "n_total": n_total}
 
     def train_from_paths(self, paths, infos: dict | None = None, *, allreduce=None, rank: int = 0,
                          world: int = 1):
@@ -655,25 +596,19 @@ class DeviceNPG:
         base_stats [mean, std, min, max] of path returns; infos updated as the reference's.
         `allreduce`, `rank`, `world`: train_from_arrays' (the paths are this rank's; the returned
         statistics too)."""
-        obs = np.concatenate([p["observations"] for p in paths])
-        act = np.concatenate([p["actions"] for p in paths])
-        adv = np.concatenate([p["advantages"] for p in paths])
+        obs, act, adv, base_stats = paths_to_arrays(paths)
         out = self.train_from_arrays(obs, act, adv, allreduce=allreduce, rank=rank, world=world)
         if infos is not None:
-            infos.update({k: v for k, v in out.items()})
-        returns = [float(np.sum(p["rewards"])) for p in paths]
-        return [float(np.mean(returns)), float(np.std(returns)), float(np.min(returns)), float(np.max(returns))]
+            infos.update(out)
+        return base_stats
 
     def train_from_engine(self, engine, advantages: torch.Tensor, *, allreduce=None, rank: int = 0,
                           world: int = 1) -> dict:
         """Update from the rollout engine's buffers without a host round trip: the recorded
         transitions obs[:T], acts[:T] ([T, B] rows) and GAE advantages [T, B].  `allreduce`, `rank`,
         `world`: train_from_arrays' (the engine's lanes are this rank's shard of the rollout)."""
-        T, B = engine.t, engine.B
-        obs = engine.obs[:T].reshape(T * B, self.S)
-        act = engine.acts[:T].reshape(T * B, self.A)
-        return self.train_from_arrays(obs, act, advantages.reshape(T * B), allreduce=allreduce, rank=rank,
-                                      world=world)
+        return self.train_from_arrays(*engine_rows(engine, advantages, self.S, self.A), allreduce=allreduce,
+                                      rank=rank, world=world)
 
 
 class NPG:
@@ -683,7 +618,7 @@ class NPG:
     policy's sizes when None).  train_step and the rollout statistics come from the reference's
     BatchREINFORCE: `class NPG(amx.NPG, BatchREINFORCE): pass`.  `allreduce` (keyword-only): the
     in-place SUM over the ranks of a sharded rollout (dist.allreduce_sum); the update is then the
-    data-parallel one over every rank's paths (DeviceNPG._train_dp), the advantages whitened on the
+    data-parallel one over every rank's paths (DeviceNPG.train_from_arrays), the advantages whitened on the
     device with the ranks' joint statistics, without a BC term, a subsampled Fisher or the dist-info
     entries of `infos`."""
 
@@ -717,8 +652,8 @@ class NPG:
         self.input_normalization = None
         self.bc_args = bc_args
         self.ctx = ctx
-        # data-parallel: `paths` are this rank's, the update the union's (DeviceNPG._train_dp; rank and
-        # world from torch.distributed's group); running_score and the rollout statistics stay per rank
+        # data-parallel: `paths` are this rank's, the update the union's (DeviceNPG.train_from_arrays; rank
+        # and world from torch.distributed's group); running_score and the rollout statistics stay per rank
         self.allreduce = allreduce
         self.device_npg = None
         self._expert = None  # (host obs, host act, device obs, device act)

@@ -28,7 +28,7 @@ import torch
 
 from . import _native as N
 from .bc import BATCH, HIDDEN, DataLog, DeviceBC, check_adam, plan_bc_batches, write_optimizer
-from .npg import NPG_EVAL, DeviceNPG, pack_policy
+from .npg import NPG_EVAL, DeviceNPG, engine_rows, pack_policy, paths_to_arrays
 
 OLD_MODES = {"snapshot": N.AMX_PPO_OLD_SNAPSHOT, "tracks_mean": N.AMX_PPO_OLD_TRACKS_MEAN}
 
@@ -134,12 +134,7 @@ class DevicePPO:
         if idx.size and (idx.min() < 0 or idx.max() >= n):
             raise ValueError(f"batches must hold row indices in [0, {n})")
         total = idx.shape[0]
-        # (adv - mean) / (std + 1e-6), population std, in fp64
-        w = torch.empty_like(adv)
-        stats = torch.empty(2, dtype=torch.float64, device=dev)
-        N.check(c.lib.amx_adv_whiten(c.h, 1, n, None, None, n, adv.data_ptr(), 1e-6, w.data_ptr(),
-                                     stats.data_ptr(), c.stream), "amx_adv_whiten")
-        adv = w
+        adv = self._npg._whiten(adv)  # (adv - mean) / (std + 1e-6), population std, in fp64
         adv32 = adv.to(torch.float32)
         tracks = self.old == "tracks_mean"
         ls_old = self.theta_old[-A:].clone()
@@ -176,22 +171,16 @@ class DevicePPO:
     def train_from_paths(self, paths, infos: dict | None = None):
         """Reference surface: mjrl path dicts (observations, actions, advantages, rewards) ->
         base_stats [mean, std, min, max] of the path returns; infos updated with the call's results."""
-        obs = np.concatenate([p["observations"] for p in paths])
-        act = np.concatenate([p["actions"] for p in paths])
-        adv = np.concatenate([p["advantages"] for p in paths])
+        obs, act, adv, base_stats = paths_to_arrays(paths)
         out = self.train_from_arrays(obs, act, adv)
         if infos is not None:
             infos.update(out)
-        returns = [float(np.sum(p["rewards"])) for p in paths]
-        return [float(np.mean(returns)), float(np.std(returns)), float(np.min(returns)), float(np.max(returns))]
+        return base_stats
 
     def train_from_engine(self, engine, advantages: torch.Tensor, **kw) -> dict:
         """Update from the rollout engine's buffers without a host round trip: the recorded
         transitions obs[:T], acts[:T] ([T, B] rows) and GAE advantages [T, B]."""
-        T, B = engine.t, engine.B
-        obs = engine.obs[:T].reshape(T * B, self.S)
-        act = engine.acts[:T].reshape(T * B, self.A)
-        return self.train_from_arrays(obs, act, advantages.reshape(T * B), **kw)
+        return self.train_from_arrays(*engine_rows(engine, advantages, self.S, self.A), **kw)
 
 
 def _shared_storage(policy) -> bool:

@@ -2,7 +2,7 @@
 restated in numpy, the collective schedule of one update (a recording all-reduce over a stubbed
 native layer: every native call returns success and leaves its buffers alone, so only the order,
 count and shapes of the messages and launches are pinned here; the numbers are the GPU tests'),
-and dist.rank_world."""
+the native calls of every variant of the one update body in order, and dist.rank_world."""
 import numpy as np
 import pytest
 import torch
@@ -75,12 +75,14 @@ S, A = 5, 3
 
 
 class _Lib:
-    def __init__(self, log):
-        self.log = log
+    def __init__(self, log, trace=None):
+        self.log, self.trace = log, trace
 
     def __getattr__(self, name):
         def call(*args):
             self.log.append(name)
+            if self.trace is not None:  # the pass entry points with their mode argument
+                self.trace.append(f"{name}:{args[1]}" if name in ("amx_npg_pass_ex", "amx_npg_pass_dp") else name)
             if name == "amx_npg_param_count":
                 return P.param_count(args[0], args[1])
             if name == "amx_npg_cg_tail_work":
@@ -93,15 +95,15 @@ class _Ctx:
     device = torch.device("cpu")
     stream, h = 0, None
 
-    def __init__(self, log):
-        self.S, self.A, self.lib = S, A, _Lib(log)
+    def __init__(self, log, trace=None):
+        self.S, self.A, self.lib = S, A, _Lib(log, trace)
 
 
-def stub_npg(log, iters):
+def stub_npg(log, iters, trace=None):
     from amp_extensions_amd.npg import DeviceNPG
     layers = [(torch.zeros(32, S), torch.zeros(32)), (torch.zeros(32, 32), torch.zeros(32)),
               (torch.zeros(A, 32), torch.zeros(A))]
-    return DeviceNPG(_Ctx(log), layers, torch.zeros(A), FIM_invert_args={"iters": iters, "damping": 1e-4})
+    return DeviceNPG(_Ctx(log, trace), layers, torch.zeros(A), FIM_invert_args={"iters": iters, "damping": 1e-4})
 
 
 @pytest.mark.parametrize("whiten", [True, False])
@@ -171,6 +173,94 @@ def test_errors_decided_before_or_right_after_the_counts():
     assert calls == [(2,)] and log == []
     with pytest.raises(ValueError):
         npg.train_from_arrays(*z, allreduce=allreduce, rank=2, world=2)
+
+
+# ---- 2b. every variant of the one update body: its native calls, in order ------------------------
+# name -> (attributes set on the DeviceNPG, train_from_arrays' keyword arguments)
+_Z4 = (np.zeros((4, S), np.float32), np.zeros((4, A), np.float32), 0.1)
+VARIANTS = {
+    "plain": ({}, {}),
+    "raw": ({}, dict(whiten=False)),
+    "cg_iters0": (dict(cg_iters=0), {}),
+    "nofold": (dict(cg_fold=False), {}),
+    "eval_before": (dict(eval_before=True), {}),
+    "dist_info": ({}, dict(dist_info=True)),
+    "bc": ({}, dict(bc=_Z4)),
+    "idx": ({}, dict(idx=np.arange(6, dtype=np.int32).reshape(3, 2))),
+    "sub0.5": (dict(hvp_subsample=0.5), {}),
+    "dp-1-0": ({}, dict(world=1, rank=0)),
+    "dp-3-1": ({}, dict(world=3, rank=1)),
+}
+DRAW_SEED = 1234
+
+
+def run_variant(name):
+    """One stubbed update at n = 7, iters = 3: (the native calls and collectives in order, the
+    result's keys, hvp_products, numpy's generator state before and after the call)."""
+    attrs, kw = VARIANTS[name]
+    trace = []
+    npg = stub_npg([], 3, trace)
+    for k, v in attrs.items():
+        setattr(npg, k, v)
+    kw = dict(kw)
+    if "world" in kw:
+        def allreduce(t):
+            trace.append("allreduce")
+            if t.dtype == torch.int64:
+                t[t == 0] = 11
+        kw["allreduce"] = allreduce
+    np.random.seed(DRAW_SEED)
+    before = np.random.get_state()
+    del trace[:]
+    with np.errstate(all="ignore"):  # the stubbed kernels leave the result buffers uninitialised
+        out = npg.train_from_arrays(np.zeros((7, S), np.float32), np.zeros((7, A), np.float32), np.zeros(7), **kw)
+    return trace, sorted(out), npg.hvp_products, before, np.random.get_state()
+
+
+# Recorded on the commit before the three update bodies and the two solves were folded into one
+# each: these are that commit's sequences, not the folded code's.
+_RED, _INIT = "amx_npg_reduce_gated", ["amx_npg_cg_init_ls", "amx_npg_cg_tail_work"]
+_VPG, _BEFORE = ["amx_npg_pass_ex:0", _RED], ["amx_npg_pass_ex:2", _RED]
+_SOLVE = _INIT + ["amx_npg_pass_ex:1", "amx_npg_cg_reduce"] + ["amx_npg_pass_cg", "amx_npg_cg_reduce"] * 2 + \
+    ["amx_npg_cg_xrp"]
+_SOLVE_IDX = _INIT + ["amx_npg_pass_idx", "amx_npg_cg_reduce"] + ["amx_npg_pass_cg_idx", "amx_npg_cg_reduce"] * 2 + \
+    ["amx_npg_cg_xrp"]
+_END = ["amx_npg_apply_step", "amx_npg_pass_ex:2", _RED]
+_LL = ["amx_npg_ll_blocks", "amx_npg_ll", _RED]
+_DP = (["allreduce", "amx_adv_whiten_parts", "allreduce", "amx_adv_whiten_apply", "amx_npg_pass_dp:0", _RED,
+        "allreduce"] + _INIT + ["amx_npg_pass_dp:1", _RED, "allreduce", "amx_npg_cg_reduce"] +
+       ["amx_npg_pass_cg_dp", _RED, "allreduce", "amx_npg_cg_reduce"] * 2 +
+       ["amx_npg_cg_xrp", "amx_npg_apply_step", "amx_npg_pass_dp:2", _RED, "allreduce"])
+_KEYS = ["advantages", "alpha", "delta", "kl_dist", "npg_grad", "surr_after", "surr_before", "vpg_grad"]
+_KEYS_EXT = sorted(_KEYS + ["hvp_products"])
+WANT = {
+    "plain": (["amx_adv_whiten"] + _VPG + _SOLVE + _END, _KEYS),
+    "raw": (_VPG + _SOLVE + _END, _KEYS),
+    "cg_iters0": (["amx_adv_whiten"] + _VPG + _INIT + _END, _KEYS),
+    "nofold": (["amx_adv_whiten"] + _VPG + _INIT + ["amx_npg_pass_ex:1", "amx_npg_cg_tail"] * 3 + _END, _KEYS),
+    "eval_before": (["amx_adv_whiten"] + _VPG + _BEFORE + _SOLVE + _END, _KEYS_EXT),
+    "dist_info": (["amx_adv_whiten"] + _VPG + _BEFORE + _SOLVE + _END + _LL * 2,
+                  sorted(_KEYS_EXT + ["lr", "new_dist_info", "old_dist_info"])),
+    "bc": (["amx_adv_whiten", "amx_npg_pass_ex:0", "amx_npg_pass_ex:0", _RED] + _BEFORE + _LL + _SOLVE + _END + _LL,
+           _KEYS_EXT),
+    "idx": (["amx_adv_whiten"] + _VPG + _BEFORE + _SOLVE_IDX + _END, _KEYS_EXT),
+    "sub0.5": (["amx_adv_whiten"] + _VPG + _BEFORE + _SOLVE_IDX + _END, _KEYS_EXT),
+    "dp-1-0": (_DP, sorted(_KEYS + ["n_total"])),
+    "dp-3-1": (_DP, sorted(_KEYS + ["n_total"])),
+}
+WANT_STATE = (624, [1234, 3159640283, 4062961311])  # np.random.seed(DRAW_SEED): position, first key words
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_native_calls_of_every_variant(name):
+    trace, keys, products, before, after = run_variant(name)
+    want_trace, want_keys = WANT[name]
+    assert trace == want_trace
+    assert keys == want_keys
+    assert products == 0
+    # (the stub's zeroed product counter: the generator is left where it was before any draw)
+    assert after[0] == before[0] and np.array_equal(after[1], before[1]) and after[2:] == before[2:]
+    assert (after[2], after[1][:3].tolist()) == WANT_STATE
 
 
 class _Model(torch.nn.Module):

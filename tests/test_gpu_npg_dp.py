@@ -261,6 +261,29 @@ def test_message_path_early_stop_bit_identical():
     assert_same_update(got, want)
 
 
+_PLAIN = {}
+
+
+@pytest.mark.parametrize("option", ["eval_before", "dist_info"])
+@pytest.mark.parametrize("N,rpb", [(33, None), (544, 96)], ids=["33", "544-rpb96"])
+def test_eval_before_or_dist_info_alone_changes_no_bit_of_the_update(N, rpb, option):
+    """eval_before alone, or dist_info alone, adds launches (surr_before's EVAL pass, the per-row
+    log-likelihoods) but no arithmetic to the update: the gradients, the step, surr_after, kl_dist
+    and the new theta are the plain update's from the same start, bit for bit."""
+    if (N, rpb) not in _PLAIN:
+        _PLAIN[N, rpb] = update(N, True, dp=False, rpb=rpb)[0]
+    want = _PLAIN[N, rpb]
+    assert want["surr_before"] == 0.0 and "hvp_products" not in want and "lr" not in want
+    npg, d = make_npg(N, rpb)
+    npg.eval_before = option == "eval_before"
+    got = npg.train_from_arrays(d["obs"], d["act"], d["adv"], dist_info=option == "dist_info")
+    torch.cuda.synchronize()
+    got["theta"] = npg.theta
+    assert got["hvp_products"] == 0 and ("lr" in got) == (option == "dist_info")
+    assert_same_update(got, want)
+    assert np.isfinite(got["theta"].cpu().numpy()).all() and not torch.equal(got["theta"], to_dev(d["theta"]))
+
+
 # ---- 3. the whitening in two halves -----------------------------------------------------------
 def whiten_parts(adv, lo, hi, rank, world, msg):
     c = ctx()
